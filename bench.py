@@ -6,6 +6,12 @@ SqExp(sig2=1, ell=0.01), jitter 1e-3, fp32, B = 32 right-hand sides per GPU = ro
 
   step          = one batched Kuu matvec over the rank's 32 RHS (hgp_toeplitz_apply, op K)
   value         = RHS-matvecs/s over all ranks (weak scaling: each rank owns 32 RHS)
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what that figure needs: set-up,
+a short settle, W warm-up steps, the K timed steps, the result line (with the roofline fraction
+the timed steps themselves give).  `--dump-outputs DIR` then writes what the last timed step
+computed (DIR/kmatvec.npy, see dump_outputs).  Everything below is measured with `--full` only:
+
   pcg_*         = compute_kn wall-clock (hipgp.py:117-146): spectrum setup + PCG(maxiter 20,
                   tol 1e-8, C^-1 preconditioner) + R^T, for the same 32 RHS
   roofline      = HBM roofline of the batched K matvec (3 pass kernels back to back) with
@@ -15,16 +21,16 @@ SqExp(sig2=1, ell=0.01), jitter 1e-3, fp32, B = 32 right-hand sides per GPU = ro
                   every host CPU as workers): K matvecs on a bounded sample, and compute_kn on
                   all 32 RHS (~30 s of CPU work), rank 0 at N=1 only
 
-The compute_kn timing and the per-pass event timing run BEFORE the timed steps (untimed for
-the metric), so the timed steps see the GPU at its steady clock.
+With `--full` the compute_kn timing and the per-pass event timing run BEFORE the timed steps
+(untimed for the metric), so the timed steps see the GPU at its steady clock.
 
 Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) WORLD_SIZE must equal --gpus;
 `python bench.py --gpus N` with no torch.distributed environment starts the N ranks itself (a
 torchrun child launched before this process touches the GPU; it exits with the child's code).
 n_gpus is the world size of the initialised process group.  RHS are sharded (each rank its own 32), no
 collective inside the timed region apart from the barriers; max-over-ranks timing.  Beside the
-weak K-matvec line, two legs measured at every N (untimed for the metric, max over ranks) that
-CAN fail to scale:
+weak K-matvec line, `--full` measures legs at every N (untimed for the metric, max over ranks)
+that CAN fail to scale:
   strong        = compute_kn for a FIXED global batch (C2's 32 RHS split 32/N per rank,
                   hipgp_amd.dist.sharded_compute_kn with the reference's all-RHS break rule:
                   one all-reduce(MIN) of a device flag per PCG iteration, RCCL on GPUs)
@@ -59,6 +65,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: compute_kn wall-clock, per-pass "
+                         "HIP-event times, the strong-scaling / ELBO-step / config-4 legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output as DIR/<name>.npy")
     ap.add_argument("--m", type=int, default=1024, help="grid points per axis (2-D)")
     ap.add_argument("--rhs", type=int, default=32)
     ap.add_argument("--pcg-reps", type=int, default=3)
@@ -113,6 +124,37 @@ def make_problem(m, B, device, seed):
     xs = torch.stack([x.reshape(-1) for x in xx], dim=-1)
     Knm = torch.cat([kf(xobs[i:i + 1], xs) for i in range(B)], dim=0).contiguous()   # (B, M)
     return grids, kf, Knm
+
+
+DUMP_BUDGET = 48 << 20   # bytes of .npy data one run writes (all ranks together)
+
+
+def dump_columns(B, M, itemsize, budget=DUMP_BUDGET, seed=0):
+    """Which columns of a (B, M) output a dump keeps: None (all of them) when the array fits the
+    budget, else a sorted, seeded sample of budget / (B * itemsize) distinct column indices --
+    the same ones for the same (B, M, itemsize, budget, seed), so two builds dump the same
+    entries."""
+    n = budget // (B * itemsize)
+    if n >= M:
+        return None
+    if n < 1:
+        raise ValueError(f"dump budget of {budget} bytes holds no column of {B} rows")
+    return np.sort(np.random.RandomState(seed).choice(M, size=n, replace=False))
+
+
+def dump_outputs(dirname, y, rank, world):
+    """Write the batched K matvec of the last timed step, y = K @ Knm^T as (B, M) float32 rows:
+    DIR/kmatvec.npy (DIR/kmatvec_rank<r>.npy per rank when there are several).  Above the budget
+    the columns dump_columns() names are kept, for every right-hand side."""
+    B, M = y.shape
+    cols = dump_columns(B, M, y.element_size(), DUMP_BUDGET // world)
+    if cols is not None:
+        y = y[:, torch.as_tensor(cols, device=y.device)]
+    a = y.detach().cpu().numpy()
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "kmatvec.npy" if world == 1 else f"kmatvec_rank{rank}.npy"), a)
 
 
 def time_events(fn, reps, stream):
@@ -484,8 +526,9 @@ def main():
         d0 = Tk.inv_matmul(Knm, do_precond=True, maxiter=20, tol=1e-8)
         return Tk._matmul_by_RT(d0)
 
+    extras = args.full and not args.kop_only     # the measurements beside the headline figure
     pcg_times = []
-    if not args.kop_only:
+    if extras:
         compute_kn()
         torch.cuda.synchronize()
         settle()
@@ -521,7 +564,7 @@ def main():
             pass_ms.append(time_events(fn, 20, stream))
 
     legs = None
-    if not args.kop_only and not args.no_legs:
+    if extras and not args.no_legs:
         legs = multi_gpu_legs(args, m, grids, kf, device, dist, world, rank, args.legs_reps)
         torch.cuda.empty_cache()
         if not args.no_c4_leg:
@@ -545,6 +588,8 @@ def main():
     dt = reduce_max(time.perf_counter() - t0)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
     if args.kop_only:
         if rank == 0:
             print(json.dumps({"kop_only": True, "value": value, "ms_per_step": ms_per_step}))
@@ -556,16 +601,6 @@ def main():
     bytes_K_rhs = 8 * M + 32 * m * h2                        # SURVEY §8(d) B_K (d=2), fp32
     bytes_launch = B * bytes_K_rhs
     achieved = bytes_launch / (ms_per_step * 1e-3) / 1e9     # driver-clock: the timed steps
-    achieved_ev = bytes_launch / (op_ms * 1e-3) / 1e9         # HIP events on the plan's stream
-    L = plan.L_K
-    pair_int = m * L[1] * 8                                  # complex intermediate per RHS pair
-    Q = (B + 1) // 2
-    pass_bytes = [Q * (2 * M * 4 + pair_int), Q * 2 * pair_int + L[0] * L[1] * 4, Q * (pair_int + 2 * M * 4)]
-    kernels = [{"pass": i, "kernel": ("rows fwd", "column conv", "rows inv")[i] if npass == 3 else str(i),
-                "ms": round(pass_ms[i], 4), "bytes": pass_bytes[i],
-                "gbs": round(pass_bytes[i] / (pass_ms[i] * 1e-3) / 1e9, 1),
-                "frac": round(pass_bytes[i] / (pass_ms[i] * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)} for i in range(npass)]
-    pcg_ms = reduce_max(float(np.median(pcg_times) * 1e3))
     traffic, traffic_src = pmc_traffic(M, B)
 
     out = {
@@ -586,9 +621,6 @@ def main():
         "config": {"workload": f"C2: 2-D {m}x{m} SqExp(1,0.01) jitter 1e-3, batched K matvec, "
                                f"{B} RHS per GPU", "M": M, "rhs_per_gpu": B, "global_rhs": B * world,
                    "parallelism": f"rhs-shard x{world}"},
-        "pcg_wall_clock_ms": pcg_ms,
-        "pcg": {"what": "compute_kn: setup + PCG(maxiter=20, tol=1e-8, precond) + R^T, B RHS",
-                "median_ms": pcg_ms, "setup_ms": setup_s * 1e3, "pcg_plus_rt_ms": solve_s * 1e3},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "achieved_note": "bytes_per_launch / ms_per_step (the timed steps' own clock)",
@@ -596,16 +628,30 @@ def main():
                                      "(rocprofv3 --pmc, 2*FETCH_SIZE + WRITE_SIZE); algorithmic "
                                      "bytes per launch = bytes_per_launch",
                      "kernel": "batched K matvec = 3 pass kernels (FWD rows, CONV cols, INV rows)",
-                     "bytes_per_launch": bytes_launch,
-                     "event_op_ms": op_ms, "event_achieved": achieved_ev,
-                     "event_frac": achieved_ev / HBM_PEAK_GBS, "passes": kernels,
-                     # the op's slowest pass-isolated kernel (the column conv at C2) with its own
-                     # algorithmic bytes and roofline fraction
-                     "dominant_pass": max(kernels, key=lambda k: k["ms"])},
+                     "bytes_per_launch": bytes_launch},
     }
+    if args.full:
+        achieved_ev = bytes_launch / (op_ms * 1e-3) / 1e9    # HIP events on the plan's stream
+        L = plan.L_K
+        pair_int = m * L[1] * 8                              # complex intermediate per RHS pair
+        Q = (B + 1) // 2
+        pass_bytes = [Q * (2 * M * 4 + pair_int), Q * 2 * pair_int + L[0] * L[1] * 4, Q * (pair_int + 2 * M * 4)]
+        kernels = [{"pass": i, "kernel": ("rows fwd", "column conv", "rows inv")[i] if npass == 3 else str(i),
+                    "ms": round(pass_ms[i], 4), "bytes": pass_bytes[i],
+                    "gbs": round(pass_bytes[i] / (pass_ms[i] * 1e-3) / 1e9, 1),
+                    "frac": round(pass_bytes[i] / (pass_ms[i] * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)} for i in range(npass)]
+        pcg_ms = reduce_max(float(np.median(pcg_times) * 1e3))
+        out["pcg_wall_clock_ms"] = pcg_ms
+        out["pcg"] = {"what": "compute_kn: setup + PCG(maxiter=20, tol=1e-8, precond) + R^T, B RHS",
+                      "median_ms": pcg_ms, "setup_ms": setup_s * 1e3, "pcg_plus_rt_ms": solve_s * 1e3}
+        # the op's slowest pass-isolated kernel (the column conv at C2) with its own algorithmic
+        # bytes and roofline fraction
+        out["roofline"].update({"event_op_ms": op_ms, "event_achieved": achieved_ev,
+                                "event_frac": achieved_ev / HBM_PEAK_GBS, "passes": kernels,
+                                "dominant_pass": max(kernels, key=lambda k: k["ms"])})
     if legs is not None:
         out.update(legs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         grids_np = [np.linspace(-1, 1, m, dtype=np.float32) for _ in range(2)]
         out["cpu_baseline"] = cpu_baseline(m, B, grids_np, seed=7, threads=args.cpu_threads)
         out["cpu_baseline"]["speedup_matvec"] = value / out["cpu_baseline"]["value"]

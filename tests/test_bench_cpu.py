@@ -45,6 +45,30 @@ def test_bench_refuses_world_size_mismatch_exit_code():
     assert "refusing" in p.stderr and "WORLD_SIZE=3" in p.stderr
 
 
+def test_dump_columns_whole_or_seeded_sample():
+    """--dump-outputs keeps a (B, M) output whole when it fits the budget, else a fixed sample of
+    its columns: distinct, sorted, in range, within the budget, the same on every call."""
+    assert bench.dump_columns(3, 1000, 4, budget=3 * 1000 * 4) is None
+    c = bench.dump_columns(3, 1000, 4, budget=3 * 1000 * 4 - 1)
+    assert len(c) == 999 and len(set(c.tolist())) == 999
+    assert (c[1:] > c[:-1]).all() and c[0] >= 0 and c[-1] < 1000
+    assert (c == bench.dump_columns(3, 1000, 4, budget=3 * 1000 * 4 - 1)).all()
+    # the default workload: 32 RHS x 1024^2 fp32 = 128 MiB, sampled down to the budget
+    c = bench.dump_columns(32, 1 << 20, 4)
+    assert 32 * 4 * len(c) <= bench.DUMP_BUDGET <= 64 << 20 and len(c) > (1 << 20) // 4
+    with pytest.raises(ValueError):
+        bench.dump_columns(8, 100, 4, budget=31)
+
+
+def test_plain_run_is_the_default():
+    sys_argv, sys.argv = sys.argv, ["bench.py"]
+    try:
+        a = bench.parse()
+    finally:
+        sys.argv = sys_argv
+    assert a.full is False and a.dump_outputs is None and a.gpus == 1
+
+
 def test_empty_shard_reports_every_phase():
     """The bench's config-4 leg barriers inside sharded_compute_kn's phase hook: a rank with no
     right-hand sides must report the same phases as the others, or the barriers would not pair."""

@@ -8,7 +8,7 @@
 # GPU step runs after a failure, a fault or a time-limit kill).  Output: gpurun_out/${TAG}_*.
 #   pytest            the whole -m gpu suite            pytest=EXPR   only tests matching -k EXPR
 #   smoke             __graft_entry__.smoke()
-#   bench             python bench.py (defaults)        bench=ARGS    with these arguments ('+' = space)
+#   bench             python bench.py --full            bench=ARGS    with these arguments too ('+' = space)
 #   bench_trim[=ARGS] the bench with HGP_POOL_MB=1024 (idle plans trimmed: per-call re-allocation)
 #   configs           tools/bench_configs.py (five-config table)
 #   phases[=C2,C4]    tools/kn_phases.py --only ...
@@ -43,7 +43,7 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1 || fail "$step" $? ${O}_smoke.log
       tail -3 ${O}_smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py $arg > ${O}_bench.json 2> ${O}_bench.err || fail "$step" $? ${O}_bench.err
+      timeout -k 10 600 python bench.py --full $arg > ${O}_bench.json 2> ${O}_bench.err || fail "$step" $? ${O}_bench.err
       python - ${O}_bench.json <<'EOF'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -56,7 +56,7 @@ EOF
     bench_trim)
       # the config-4 leg with the idle-plan pool forced to trim (HGP_POOL_MB=1024): every call
       # re-allocates the plan's scratch, as round 5's 62 GB C4 plan did under the 1/8 budget
-      HGP_POOL_MB=1024 timeout -k 10 600 python bench.py --no-cpu-baseline $arg > ${O}_bench_trim.json 2> ${O}_bench_trim.err \
+      HGP_POOL_MB=1024 timeout -k 10 600 python bench.py --full --no-cpu-baseline $arg > ${O}_bench_trim.json 2> ${O}_bench_trim.err \
         || fail "$step" $? ${O}_bench_trim.err
       python -c "import json,sys; d=json.loads(open('${O}_bench_trim.json').read().strip().splitlines()[-1]); print('trimmed pool C4 leg:', json.dumps(d.get('strong_c4')))" ;;
     configs)

@@ -9,7 +9,7 @@ TAG=${1:-run}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT" -o run --output-format csv -- \
-  python3 bench.py ${BENCH_ARGS:---no-cpu-baseline --steps 20 --warmup 5 --pcg-reps 2} > "$OUT/bench.log" 2>&1
+  python3 bench.py ${BENCH_ARGS:---full --no-cpu-baseline --steps 20 --warmup 5 --pcg-reps 2} > "$OUT/bench.log" 2>&1
 rc=$?
 echo "[profile] rocprofv3 exit=$rc"
 f=$(find "$OUT" -name "*kernel_stats.csv" | head -1)
