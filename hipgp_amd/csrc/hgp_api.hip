@@ -125,6 +125,8 @@ struct hgp_plan {
   DevBuf r, z, p, Ap, part_op, part_u, part_f, scal, flags, bT, xT;
   // slab-sharded PCG (hgp_slab_cg_*): fused-dot / update partials and per-RHS alpha / beta
   DevBuf slab_part, slab_coef;
+  // hgp_rt_stats: the fused epilogue's partials, and one piece of kn on the plans that materialise it
+  DevBuf st_part, st_kn;
   int64_t cg_nrhs = 0;
   int cg_precond = 0, cg_layout = 0;
   void* cg_x_user = nullptr;
@@ -202,7 +204,7 @@ struct hgp_plan {
       bsPre[a].release(); bsPost[a].release(); bsFilt[a].release();
     }
     DevBuf* bufs[] = {&specK, &specI, &specR, &specRg, &specKg, &gridA, &gridB, &Dm3, &nclamp, &ws1, &ws2, &set1, &set2, &setM1, &setM2, &setC,
-                      &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT};
+                      &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 3; ++i) {
       if (side[i]) (void)hipStreamDestroy(side[i]);
@@ -310,6 +312,14 @@ struct RowEpi {
   int fix = 0;                   // EPI_XP: PassDesc::cg_fix
 };
 
+// Prediction statistics in place of R^T's output (hgp_rt_stats): the last pass runs EPI_STATS
+// against the shared M'-vectors qm / qs, and each RHS chunk's partials are finished into out3
+struct RowStats {
+  const void* qm;
+  const void* qs;
+  void* out3;
+};
+
 // the chunk (first RHS q0) view of an epilogue's in-kernel CG scalar
 template <typename T>
 void set_cg_scalar(PassDesc& D, const RowEpi* epi, int64_t q0) {
@@ -400,12 +410,22 @@ bool grid_route(const hgp_plan* P, int op) {
   return (op == HGP_OP_R || op == HGP_OP_RT) ? P->grid_r : P->grid_k;
 }
 
+// whether R^T of this plan ends in the row-inverse kernel (the 2-D / 3-D row-pair sequences of
+// run_op), whose EPI_STATS epilogue hgp_rt_stats fuses; 1-D plans, the full-grid route and rows
+// beyond one CU's LDS (the generic sequences) materialise kn a piece at a time instead
+template <typename T>
+bool rt_stats_fused(const hgp_plan* P) {
+  if (P->d < 2 || grid_route(P, HGP_OP_RT)) return false;
+  if (P->d == 2) return rowt_fits<T>((int)(P->LR[1] / 2), 1) != 0;
+  return rowt_fits<T>((int)(P->LR[2] / 2), 0) != 0 && linet_fits<T>((int)(P->LR[1] / 2)) != 0;
+}
+
 template <typename T>
 int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void* dotv, void* partial,
            const int* done, int only_pass = -1, void* spart = nullptr, const RowEpi* epi = nullptr,
-           const MidFn* mid = nullptr, const PairOp* pair = nullptr) {
+           const MidFn* mid = nullptr, const PairOp* pair = nullptr, const RowStats* stats = nullptr) {
   if (grid_route(P, op)) {
-    if (spart != nullptr || epi != nullptr || mid != nullptr || only_pass >= 0)
+    if (spart != nullptr || epi != nullptr || mid != nullptr || only_pass >= 0 || stats != nullptr)
       return fail(HGP_E_UNSUPPORTED, "internal: the full-grid route has no fused PCG epilogue or pass split");
     // after the break (`done` set) every transform / embed / crop kernel of the route is a device
     // no-op, so the iterations up to maxiter cost launches only; the dot partials it may still
@@ -427,7 +447,9 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
   const int G2 = (d == 2 && !gen2) ? rowt_group<T>((int)(g.L[1] / 2)) : 1;
   const int64_t S0 = (d >= 2) ? round_up(std::max(g.in[0], g.out[0]), 16) : 0;   // axis-0 pitch
   if (d == 2) B1 = gen2 ? std::max(g.in[0], g.out[0]) * Sl : (g.L[1] / 2 + G2) / G2 * G2 * S0;
-  if (gen2 && (spart != nullptr || epi != nullptr || mid != nullptr))
+  if (stats != nullptr && (d == 1 || op != HGP_OP_RT || epi != nullptr || pair != nullptr || only_pass >= 0))
+    return fail(HGP_E_ARG, "internal: the statistics epilogue is R^T's, on the 2-D / 3-D row-pair sequences");
+  if (gen2 && (spart != nullptr || epi != nullptr || mid != nullptr || stats != nullptr))
     return fail(HGP_E_ARG, "internal: the generic 2-D sequence has no fused PCG epilogue");
   if (pair != nullptr && (d != 2 || gen2 || epi == nullptr || epi->mode != EPI_R || only_pass >= 0))
     return fail(HGP_E_ARG, "internal: a chained operator needs the 2-D row-pair sequence and an EPI_R epilogue");
@@ -445,7 +467,7 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
     // the axis-0 / middle passes address one RHS's W2 with 32-bit element offsets
     if (B2 >= ((int64_t)1 << 31)) return fail(HGP_E_UNSUPPORTED, "3-D grid too large: one right-hand side's intermediate exceeds 2^31 values");
   }
-  if (gen3 && (spart != nullptr || epi != nullptr || mid != nullptr))
+  if (gen3 && (spart != nullptr || epi != nullptr || mid != nullptr || stats != nullptr))
     return fail(HGP_E_ARG, "internal: the generic 3-D sequence has no fused PCG epilogue");
   // the 2-D row passes address one RHS's intermediate slab (and the contiguous pass one line)
   // with 32-bit byte offsets from a scalar base (raw buffer accesses, hgp_rows.hpp)
@@ -486,6 +508,9 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
   // fused-dot partials per RHS: one per output row pair (3-D: per pair of each i0 plane)
   const int64_t rows_out = (d == 1) ? 1 : (d == 2 ? g.out[0] : g.out[0] * g.out[1]);
   const int64_t rn_last = (d == 1) ? 1 : (d == 3 && !gen3) ? g.out[0] * ((g.out[1] + 1) / 2) : (rows_out + 1) / 2;
+  // statistics partials [slot][q][rn_last][3]: a chunk's are finished on its stream before the
+  // slot's next chunk overwrites them
+  if (stats != nullptr) HGP_TRY(P->st_part.ensure((size_t)(NS * Qc * rn_last * 3) * sizeof(T)));
 
   // chunk j of nch: RHS [j nrhs / nch, (j + 1) nrhs / nch).  Balanced (HGP_BALANCED_CHUNKS=1): nch = ceil(nrhs /
   // Qc) rounded up to a multiple of NS and sizes that differ by at most one, so the NS streams get
@@ -512,6 +537,17 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
     T* yo = yout + q0 * g.out_M;
     const T* dvc = dv ? dv + q0 * g.out_M : nullptr;
     T* pc = part ? part + q0 * rn_last : nullptr;
+    T* spc = stats ? reinterpret_cast<T*>(P->st_part.ptr) + (int64_t)slot * Qc * rn_last * 3 : nullptr;
+    auto stats_desc = [&](PassDesc& D) {
+      D.out.ptr = nullptr;                      // nothing is stored
+      D.dot = nullptr; D.partial = nullptr;
+      D.st_qm = stats->qm; D.st_qs = stats->qs; D.st_part = spc;
+    };
+    auto stats_finish = [&]() -> int {
+      hipError_t e = rowdots_finish(P->dtype, spc, (int)rn_last, qn, reinterpret_cast<T*>(stats->out3) + q0 * 3, st);
+      if (e != hipSuccess) return fail(HGP_E_HIP, std::string("statistics finish: ") + hipGetErrorString(e));
+      return 0;
+    };
 
     if (d == 1) {
       PassDesc D = base_desc();
@@ -627,7 +663,11 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
         Cd.cg_part = epi->part ? reinterpret_cast<T*>(epi->part) + q0 * nrb : nullptr;
         set_cg_scalar<T>(Cd, epi, q0);
       }
-      if (pair == nullptr) {
+      if (stats != nullptr) {
+        stats_desc(Cd);
+        HGP_TRY(run_rowt(1, Cd, EPI_STATS));
+        HGP_TRY(stats_finish());
+      } else if (pair == nullptr) {
         HGP_TRY(run_rowt(1, Cd, epi_mode));
       } else {
         // K's row inverse also leaves the forward row transform of the new r in w1 (EPI_RF);
@@ -722,7 +762,14 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
         E.cg_part = epi->part ? reinterpret_cast<T*>(epi->part) + q0 * g.out[0] * nrb : nullptr;
         set_cg_scalar<T>(E, epi, q0);
       }
-      HGP_TRY(run_rowt(1, E, epi_mode));
+      if (stats != nullptr) {
+        stats_desc(E);
+        E.cg_div = (int)g.out[0];                 // qm / qS plane of kernel line q: q % out[0]
+        HGP_TRY(run_rowt(1, E, EPI_STATS));
+        HGP_TRY(stats_finish());
+      } else {
+        HGP_TRY(run_rowt(1, E, epi_mode));
+      }
     } else {
       C2<T>* w1 = reinterpret_cast<C2<T>*>(P->ws1.ptr) + (int64_t)slot * Qc * B1;
       C2<T>* w2 = reinterpret_cast<C2<T>*>(P->ws2.ptr) + (int64_t)slot * Qc * B2;
@@ -1477,6 +1524,35 @@ int pcg_finish_x(hgp_plan* P) {
   return 0;
 }
 
+// kn values the materialising route of hgp_rt_stats holds at a time (at least one RHS)
+#ifndef HGP_RT_STATS_PIECE
+#define HGP_RT_STATS_PIECE ((int64_t)32 << 20)
+#endif
+
+// out3[n] = (kn_n . qm, |kn_n|^2, kn_n^2 . qS), kn_n = R^T d_n never stored: R^T's sequence with the
+// EPI_STATS row inverse last, RHS-chunked as the op itself.  Plans whose R^T does not end in that
+// kernel (rt_stats_fused) run R^T into plan scratch one bounded piece of RHS at a time and reduce
+// each piece with meanfield_rowdots: peak extra memory is one piece, never nrhs x M'.
+template <typename T>
+int rt_stats_t(hgp_plan* P, const void* dv, int64_t nrhs, const void* qm, const void* qS, void* out3) {
+  if (rt_stats_fused<T>(P)) {
+    const RowStats st{qm, qS, out3};
+    return run_op<T>(P, HGP_OP_RT, dv, nullptr, nrhs, nullptr, nullptr, nullptr, -1, nullptr, nullptr, nullptr, nullptr,
+                     &st);
+  }
+  const int64_t piece = std::max<int64_t>(1, std::min<int64_t>(nrhs, HGP_RT_STATS_PIECE / P->Mp));
+  HGP_TRY(P->st_kn.ensure((size_t)(piece * P->Mp) * sizeof(T)));
+  for (int64_t q0 = 0; q0 < nrhs; q0 += piece) {
+    const int64_t qn = std::min(piece, nrhs - q0);
+    HGP_TRY(run_op<T>(P, HGP_OP_RT, reinterpret_cast<const T*>(dv) + q0 * P->M, P->st_kn.ptr, qn, nullptr, nullptr,
+                      nullptr));
+    hipError_t e = meanfield_rowdots(P->dtype, P->st_kn.ptr, qn, P->Mp, qm, qS, reinterpret_cast<T*>(out3) + q0 * 3,
+                                     P->stream);
+    if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rt_stats: ") + hipGetErrorString(e));
+  }
+  return 0;
+}
+
 #define DISPATCH(P, FN, ...) ((P)->dtype == HGP_F64 ? FN<double>(__VA_ARGS__) : FN<float>(__VA_ARGS__))
 
 int check_plan(const hgp_plan* P) {
@@ -1694,6 +1770,17 @@ int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t n
   P->graph_key = key;
   HIP_TRY(hipGraphLaunch(exec, P->stream));
   return 0;
+}
+
+int hgp_rt_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, const void* qS, void* out3) {
+  HGP_TRY(check_plan(plan));
+  if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  if (nrhs < 0) return fail(HGP_E_ARG, "hgp_rt_stats: nrhs < 0");
+  if (nrhs == 0) return 0;
+  if (d == nullptr || qm == nullptr || qS == nullptr || out3 == nullptr)
+    return fail(HGP_E_ARG, "hgp_rt_stats: null d / qm / qS / out3");
+  HGP_TRY(use_device(plan));
+  return DISPATCH(plan, rt_stats_t, plan, d, nrhs, qm, qS, out3);
 }
 
 int hgp_toeplitz_apply_pass(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs, int pass) {
@@ -2204,7 +2291,7 @@ int64_t plan_scratch_bytes(const hgp_plan* P) {
   const DevBuf* bufs[] = {&P->ws1, &P->ws2, &P->set1, &P->set2, &P->setM1, &P->setM2, &P->setC, &P->r, &P->z,
                           &P->p, &P->Ap, &P->part_op, &P->part_u, &P->part_f, &P->scal, &P->bT, &P->xT,
                           &P->gridA, &P->gridB,    // the full-grid R / R^T buffers (grid_r plans)
-                          &P->slab_part, &P->slab_coef};
+                          &P->slab_part, &P->slab_coef, &P->st_part, &P->st_kn};
   int64_t b = 0;
   for (const DevBuf* d : bufs) b += (int64_t)d->bytes;
   return b;
@@ -2235,7 +2322,7 @@ int hgp_plan_trim(hgp_plan* plan) {
   DevBuf* bufs[] = {&plan->ws1, &plan->ws2, &plan->set1, &plan->set2, &plan->setM1, &plan->setM2, &plan->setC,
                     &plan->r, &plan->z, &plan->p, &plan->Ap, &plan->part_op, &plan->part_u, &plan->part_f,
                     &plan->scal, &plan->bT, &plan->xT, &plan->gridA, &plan->gridB, &plan->slab_part,
-                    &plan->slab_coef};
+                    &plan->slab_coef, &plan->st_part, &plan->st_kn};
   for (DevBuf* b : bufs) b->release();
   plan->drop_graph();                               // its kernels addressed the freed workspaces
   plan->last_apply = hgp_plan::ApplyKey();

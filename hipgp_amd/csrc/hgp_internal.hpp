@@ -92,6 +92,7 @@ hipError_t meanfield_stats(int dtype, const void* kn, int64_t nrhs, int64_t Mp, 
                            void* dm, hipStream_t s);
 hipError_t meanfield_rowdots(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* qm, const void* qS,
                              void* out3, hipStream_t s);
+hipError_t rowdots_finish(int dtype, const void* part, int np, int64_t nrhs, void* out3, hipStream_t s);
 hipError_t meanfield_cols(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* iv, const void* bdiff,
                           void* lam, void* dm, hipStream_t s);
 // expanded grid n[a] tiled by blocks of side b[a] (nb[a] per axis); bs points per block, nbw

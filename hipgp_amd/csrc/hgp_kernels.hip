@@ -440,11 +440,16 @@ __device__ __forceinline__ T block_sum_det(T v, T* red) {
   return s;
 }
 
-// x <- 0, r <- b (row layout)
+// x <- 0, r <- b (row layout).  b and x may be the same buffer (a solve in place of its right-hand
+// side, hgp_pcg_begin): each element of b is read before x's is written, and b is not read again
 template <typename T>
-__global__ void k_cg_init(const T* __restrict__ b, T* __restrict__ x, T* __restrict__ r, int64_t n) {
+__global__ void k_cg_init(const T* b, T* x, T* __restrict__ r, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { x[i] = (T)0; r[i] = b[i]; }
+  if (i < n) {
+    const T v = b[i];
+    x[i] = (T)0;
+    r[i] = v;
+  }
 }
 
 template <typename T>

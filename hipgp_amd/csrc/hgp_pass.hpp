@@ -162,8 +162,11 @@ enum { SPEC_REAL = 0, SPEC_CPLX = 1, SPEC_CPLX_CONJ = 2 };
 // preconditioner the x update is deferred to the C^-1 pass: EPI_R r update, EPI_XP x and p
 // EPI_RF: EPI_R, then the forward row transform of the updated r rows (the first pass of the
 // C^-1 r that follows in the same PCG iteration) into the block's rows of the intermediate
-enum { EPI_OUT = 0, EPI_XR = 1, EPI_R = 2, EPI_XP = 3, EPI_RF = 4 };
+// EPI_STATS: nothing is stored; each row pair leaves the three prediction dots of its outputs y with
+// the shared M'-vectors qm / qS (sum y qm, sum y^2, sum y^2 qS; PassDesc::st_*)
+enum { EPI_OUT = 0, EPI_XR = 1, EPI_R = 2, EPI_XP = 3, EPI_RF = 4, EPI_STATS = 5 };
 constexpr bool epi_r(int e) { return e == EPI_R || e == EPI_RF; }
+constexpr bool epi_cg(int e) { return e != EPI_OUT && e != EPI_STATS; }   // the fused PCG updates
 
 struct View {
   void* ptr;
@@ -219,6 +222,11 @@ struct PassDesc {
   int cg_np;
   const void* cg_rs;
   void* cg_rs_out;
+  // EPI_STATS (hgp_rows.hpp): qm and qS laid out as ONE right-hand side's output (shared by all
+  // RHS: rows at out.r_stride; 3-D: plane q % cg_div at out.q_stride), partials [q][Rn][3]
+  const void* st_qm;
+  const void* st_qs;
+  void* st_part;
 };
 
 constexpr int LDS_CAP = 160 * 1024;

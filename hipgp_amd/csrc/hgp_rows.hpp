@@ -597,7 +597,7 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
   // latency hides under the tile's) and summed per thread and per wave right after it lands;
   // the wave sums are combined in the epilogue (cg_scalar)
   T csum = 0;
-  if constexpr (EPI != EPI_OUT) {
+  if constexpr (epi_cg(EPI)) {
     if (d.cg_sp != nullptr) {   // uniform
       const int qc = d.cg_div > 1 ? q / d.cg_div : q;
       const T* sp = reinterpret_cast<const T*>(d.cg_sp) + (int64_t)qc * d.cg_np;
@@ -629,7 +629,7 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
 
   // combine: y[p] = ye + conj(W_L^p) yo, y[p+H] = ye - conj(W_L^p) yo; real rows out
   const int out_len = d.out.len;
-  if constexpr (EPI != EPI_OUT) {
+  if constexpr (epi_cg(EPI)) {
     // PCG epilogue: stage the block's 2C output rows in LDS, then update the CG vectors in
     // one coalesced sweep (y itself never goes to HBM)
     T* ys = reinterpret_cast<T*>(smem_raw);
@@ -734,6 +734,102 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
       __syncthreads();   // ys consumed: the exchange images overlay it
       row_fwd_tail<T, H, P, G, HGP_RF_SEQ, Cfg>(fa, fb, lds, tab, twg, t, l, lbase, const_cast<C2<T>*>(W), S0, row0, nrow_blk,
                                            d.dcny > 0);
+    }
+    return;
+  }
+  if constexpr (EPI == EPI_STATS) {
+    // Prediction statistics: the pair's outputs y are formed as below and never stored; they leave
+    // sum y qm, sum y^2 and sum y^2 qS (row a, then row b, per position) in partial [q][Rn][3].
+    // qm / qS are one RHS's output layout shared by every RHS: the row's base takes no q (3-D: the
+    // plane q % cg_div).  The three branches are EPI_OUT's below; the selects keep a cropped
+    // position, an absent pair (its transform ran on pair 0's data) and an absent second row (its
+    // imaginary part is rounding noise, not zero) out of the sums.
+    const int64_t pl = d.cg_div > 1 ? (int64_t)(q % d.cg_div) * d.out.q_stride : 0;
+    const int64_t ro = pl + (int64_t)(pvalid ? 2 * rp : 0) * d.out.r_stride;
+    const T* qm_a = reinterpret_cast<const T*>(d.st_qm) + ro;
+    const T* qs_a = reinterpret_cast<const T*>(d.st_qs) + ro;
+    T s0 = 0, s1 = 0, s2 = 0;
+    auto acc = [&](T ya, T yb, T ma, T mb, T sa, T sb) {
+      const T ya2 = ya * ya, yb2 = yb * yb;
+      s0 += ya * ma; s1 += ya2; s2 += ya2 * sa;
+      s0 += yb * mb; s1 += yb2; s2 += yb2 * sb;
+    };
+    int tt = t;
+    asm volatile("" : "+v"(tt));
+    if constexpr (TT % 64 == 0) {
+      // wave-uniform pair: the rows' scalar bases as buffer resources whose range crops positions
+      // past out_len (their qm / qS read 0) and an absent pair / second row
+      const uint32_t rowb = (uint32_t)out_len * (uint32_t)sizeof(T);
+      const BufRsrc ma = buf_rsrc(qm_a, pvalid ? rowb : 0u), mb = buf_rsrc(qm_a + d.out.r_stride, has2 ? rowb : 0u);
+      const BufRsrc sa = buf_rsrc(qs_a, pvalid ? rowb : 0u), sb = buf_rsrc(qs_a + d.out.r_stride, has2 ? rowb : 0u);
+      const uint32_t lo = (uint32_t)tt * (uint32_t)sizeof(T);
+#pragma unroll
+      for (int k = 0; k < P; ++k) {
+        const int p = tt + TT * k;
+        const C2<T> wo = cmulc<T>(vb[k], tw_at<T, H>(tab, p));
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          if (hh * H < out_len) {               // uniform: does this half reach the output at all
+            const C2<T> y = hh == 0 ? cadd<T>(va[k], wo) : csub<T>(va[k], wo);
+            const uint32_t so = (uint32_t)(TT * k + hh * H) * (uint32_t)sizeof(T);
+            const bool in = p + hh * H < out_len;
+            acc((in && pvalid) ? y.x : (T)0, (in && has2) ? y.y : (T)0, buf_ld<T>(ma, lo, so), buf_ld<T>(mb, lo, so),
+                buf_ld<T>(sa, lo, so), buf_ld<T>(sb, lo, so));
+          }
+        }
+      }
+    } else if constexpr (std::is_same<T, float>::value) {
+      // several pairs per wave: one resource from the block's first row, per-lane 32-bit offsets,
+      // masked positions sent past the range (they read 0)
+      const int64_t bo = pl + (int64_t)(2 * rb * C) * d.out.r_stride;
+      const BufRsrc rm = buf_rsrc(reinterpret_cast<const T*>(d.st_qm) + bo, 0x7fffffffu);
+      const BufRsrc rs = buf_rsrc(reinterpret_cast<const T*>(d.st_qs) + bo, 0x7fffffffu);
+      const uint32_t rowa = (uint32_t)(2 * l) * (uint32_t)d.out.r_stride, rowp = (uint32_t)d.out.r_stride;
+      constexpr uint32_t DROP = 0x80000000u;
+#pragma unroll
+      for (int k = 0; k < P; ++k) {
+        const int p = tt + TT * k;
+        const C2<T> wo = cmulc<T>(vb[k], tw_at<T, H>(tab, p));
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          if (hh * H < out_len) {
+            const C2<T> y = hh == 0 ? cadd<T>(va[k], wo) : csub<T>(va[k], wo);
+            const int pp = p + hh * H;
+            const bool in = pvalid && pp < out_len;
+            const uint32_t oa = in ? (rowa + (uint32_t)pp) * (uint32_t)sizeof(T) : DROP;
+            const uint32_t ob = (in && has2) ? (rowa + rowp + (uint32_t)pp) * (uint32_t)sizeof(T) : DROP;
+            acc(in ? y.x : (T)0, (in && has2) ? y.y : (T)0, buf_ld<T>(rm, oa), buf_ld<T>(rm, ob), buf_ld<T>(rs, oa),
+                buf_ld<T>(rs, ob));
+          }
+        }
+      }
+    } else {
+      // plain branch (fp64 rows of several pairs per wave: reference-precision runs)
+      const T* qm_b = qm_a + d.out.r_stride;
+      const T* qs_b = qs_a + d.out.r_stride;
+#pragma unroll
+      for (int k = 0; k < P; ++k) {
+        const int p = tt + TT * k;
+        const C2<T> wo = cmulc<T>(vb[k], tw_at<T, H>(tab, p));
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          const C2<T> y = hh == 0 ? cadd<T>(va[k], wo) : csub<T>(va[k], wo);
+          const int pp = p + hh * H;
+          if (pvalid && pp < out_len) {
+            if (has2) acc(y.x, y.y, qm_a[pp], qm_b[pp], qs_a[pp], qs_b[pp]);
+            else acc(y.x, (T)0, qm_a[pp], (T)0, qs_a[pp], (T)0);
+          }
+        }
+      }
+    }
+    // block sums in line_sum's order, one after the other through the same wave-sum area
+    T* red = reinterpret_cast<T*>(smem_raw);
+    s0 = line_sum<T, TT>(s0, red);
+    s1 = line_sum<T, TT>(s1, red);
+    s2 = line_sum<T, TT>(s2, red);
+    if (t == 0 && pvalid) {
+      T* po = reinterpret_cast<T*>(d.st_part) + ((int64_t)q * d.Rn + rp) * 3;
+      po[0] = s0; po[1] = s1; po[2] = s2;
     }
     return;
   }

@@ -181,6 +181,18 @@ hipError_t meanfield_rowdots_t(const void* kn, int64_t nrhs, int64_t Mp, const v
   return hipFreeAsync(part, s);
 }
 
+// the finish alone, on partials [nrhs][np][3] another kernel left (the row-inverse pass's EPI_STATS
+// epilogue, hgp_rows.hpp): out3[n * 3 + c], fixed order
+hipError_t rowdots_finish(int dtype, const void* part, int np, int64_t nrhs, void* out3, hipStream_t s) {
+  if (nrhs == 0) return hipSuccess;
+  const dim3 grid((unsigned)((nrhs + 3) / 4)), block(256);
+  if (dtype == HGP_F64)
+    hipLaunchKernelGGL((k_rowdots_finish<double>), grid, block, 0, s, (const double*)part, np, (int)nrhs, (double*)out3);
+  else
+    hipLaunchKernelGGL((k_rowdots_finish<float>), grid, block, 0, s, (const float*)part, np, (int)nrhs, (float*)out3);
+  return hipGetLastError();
+}
+
 template <typename T>
 hipError_t meanfield_cols_t(const void* kn, int64_t nrhs, int64_t Mp, const void* iv, const void* bdiff, void* lam,
                             void* dm, hipStream_t s) {

@@ -180,6 +180,27 @@ class ToeplitzPlan:
             self._report_ws()
         return out
 
+    def rt_stats(self, d, qm, qS):
+        """(B, 3) rows (kn.qm, |kn|^2, kn^2.qS) of kn = R^T d without materialising the (B, M') kn
+        (hgp_rt_stats): d (B, M), qm / qS (M',) or (M', 1).  Deterministic."""
+        d = self._vec(d, "d", self.M)
+        vecs = []
+        for t, name in ((qm, "qm"), (qS, "qS")):
+            _lib.require_device_tensor(t, name)
+            if t.dtype != self.dtype or t.device != self.device:
+                raise TypeError(f"{name} is {t.dtype} on {t.device}, plan is {self.dtype} on {self.device}")
+            if t.numel() != self.Mprime:
+                raise ValueError(f"{name} has {t.numel()} values, expanded grid has M'={self.Mprime}")
+            vecs.append(t.detach().reshape(-1).contiguous())
+        out = torch.empty((d.shape[0], 3), dtype=self.dtype, device=self.device)
+        self._bind_stream()
+        check(lib().hgp_rt_stats(self._h, ctypes.c_void_p(d.data_ptr()), d.shape[0],
+                                 ctypes.c_void_p(vecs[0].data_ptr()), ctypes.c_void_p(vecs[1].data_ptr()),
+                                 ctypes.c_void_p(out.data_ptr())))
+        if not _ws_warned:
+            self._report_ws()
+        return out
+
     def column_grad(self, op, x, g):
         """d/dcolumn of sum(g * op(x)) through the operator's spectrum (hgp_plan_column_grad),
         (M,) in the plan dtype; x, g shaped like op's input / output (`toeplitz_tensor.py:20-125`)."""

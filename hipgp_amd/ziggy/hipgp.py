@@ -26,6 +26,8 @@ UnboundLocalError at `hipgp.py:314` fixed (parity pinned by the oracle restateme
 Not built (OUT of the hot path): the full-rank variational family
 (`FullRankToeplitzGP`, `hipgp.py:693-797`: a dense M' x M' covariance, 70 TB at C2).
 """
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -137,6 +139,11 @@ class ToeplitzInducingGP(SviGP):
 
     def compute_knSkn(self, kn, qS):
         raise NotImplementedError
+
+    def predict_stats(self, Knm, maxiter_cg=50, Kmm=None):
+        """(bsz, 3) rows (kn.qm, kn.kn, kn S kn) for `predict(fused=True)` without kn itself, or
+        None where the family (or the whitening, or a caller's Kmm) has no fused route."""
+        return None
 
     def get_kl_to_prior(self, qm, qS):
         raise NotImplementedError
@@ -291,12 +298,26 @@ class ToeplitzInducingGP(SviGP):
         return torch.mean(an) - self.get_kl_to_prior(qm, qS) / self.N
 
     def predict(self, x, integrated_obs=False, semi_integrated_estimator="analytic",
-                semi_integrated_samps=10, maxiter_cg=50, Kmm=None):
-        """E[f(x)] and sd[f(x)] (`hipgp.py:416-446`), returned on the CPU."""
+                semi_integrated_samps=10, maxiter_cg=50, Kmm=None, fused=None):
+        """E[f(x)] and sd[f(x)] (`hipgp.py:416-446`), returned on the CPU.
+
+        fused=True takes kn.qm, |kn|^2 and kn^2.qS straight from the R^T pass (hgp_rt_stats) where
+        the family has them (`predict_stats`), so the (bsz, M') kn and its temporaries are never
+        allocated; families without it take the materialised path.  None reads HGP_PREDICT_FUSED
+        (default off)."""
+        if fused is None:
+            fused = os.environ.get("HGP_PREDICT_FUSED", "0") not in ("", "0")
         x = x.to(self.xgrids[0].device)
         Knm, Knn_diag = self._make_grams(x, integrated_obs=integrated_obs,
                                          semi_integrated_estimator=semi_integrated_estimator,
                                          semi_integrated_samps=semi_integrated_samps)
+        out3 = self.predict_stats(Knm, maxiter_cg=maxiter_cg, Kmm=Kmm) if fused else None
+        if out3 is not None:
+            qm, _ = self.standard_variational_params()
+            mu = out3[:, 0].reshape(-1, *qm.shape[1:])
+            ktilde = (Knn_diag - out3[:, 1]).clamp_min(1e-5)
+            sig = torch.sqrt(ktilde + out3[:, 2])[:, None]
+            return mu.cpu().detach(), sig.cpu().detach()
         kn = self.compute_kn(Knm, maxiter_cg=maxiter_cg, Kmm=Kmm)
         qm, qS = self.standard_variational_params()
         mu = kn.matmul(qm)
@@ -350,6 +371,27 @@ class MeanFieldToeplitzGP(ToeplitzInducingGP):
 
     def compute_knSkn(self, kn, qS):
         return torch.sum(kn * kn * qS.t(), dim=-1).squeeze()
+
+    def predict_stats(self, Knm, maxiter_cg=50, Kmm=None):
+        """Diagonal S: the three dots are ToeplitzTensor.rt_stats (hgp_rt_stats) on the PCG solution,
+        with compute_kn's PCG settings; Knm is consumed (the solve overwrites it where it can).  None,
+        with Knm untouched, for cholesky whitening or a Kmm without rt_stats."""
+        if self.whitened_type != 'ziggy':
+            return None
+        if Kmm is None:
+            Kmm = self.toeplitz()
+        if not hasattr(Kmm, "rt_stats"):
+            return None
+        with torch.no_grad():
+            # Knm is the caller's to consume (predict made it for this call): the solve overwrites it
+            # where the tensor allows, so no second (bsz, M) tensor is held beside it
+            if hasattr(Kmm, "inv_matmul_") and Knm.is_contiguous() and not Knm.requires_grad \
+                    and not Kmm.column.requires_grad:
+                d0 = Kmm.inv_matmul_(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
+            else:
+                d0 = Kmm.inv_matmul(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
+            qm, qS = self.standard_variational_params()
+            return Kmm.rt_stats(d0, qm, qS)
 
     # ---- natural gradient as batch sums + update (sharding-friendly) ------------------------
     def batch_stats(self, kn, ybatch, Knn_diag, noise_std_batch=None):

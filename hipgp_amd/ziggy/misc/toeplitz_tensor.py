@@ -5,6 +5,7 @@ Operator map (reference line -> here):
   __init__ spectrum setup (:12-33)      -> ToeplitzPlan.set_column  (hgp_plan_set_column)
   _matmul_by_K     (:70-83)             -> HGP_OP_K
   _matmul_by_RT    (:85-97)             -> HGP_OP_RT
+  rt_stats (no reference line)          -> hgp_rt_stats (R^T with predict's three dots fused in)
   _matmul_by_R     (:99-112)            -> HGP_OP_R
   _matmul_by_Cinv  (:114-125)           -> HGP_OP_CINV
   _solve / conj_grad2 (:54-68)          -> hgp_pcg_solve (device-side early-exit flag)
@@ -70,6 +71,15 @@ class ToeplitzTensor:
         """compute A^{-1}R, where self = A  (`toeplitz_tensor.py:47-52`)"""
         return InvMatmul.apply(self, self.column, right_tensor, do_precond, maxiter, tol)
 
+    def inv_matmul_(self, right_tensor, do_precond=True, maxiter=20, tol=1e-8):
+        """`inv_matmul` in place of `right_tensor` (bsz, M), which it returns holding A^{-1}R: the
+        same PCG without a second (bsz, M) tensor (hgp_pcg_solve with x = b).  No autograd."""
+        assert right_tensor.ndimension() == 2, right_tensor.ndimension()
+        if right_tensor.requires_grad or self.column.requires_grad or not right_tensor.is_contiguous():
+            raise RuntimeError("inv_matmul_ needs a contiguous right_tensor and no grad-requiring input")
+        self.set_batch_shape(right_tensor.shape[:-1])
+        return self._plan.pcg(right_tensor, maxiter, tol, precond=do_precond, out=right_tensor)
+
     def _solve(self, vec, do_precond=True, maxiter=100, tol=1e-8, callback=None):
         """vec: (bsz, M) -> K^{-1} vec by PCG (`toeplitz_tensor.py:54-68`)."""
         assert len(vec.shape) == 2
@@ -95,6 +105,14 @@ class ToeplitzTensor:
     def _matmul_by_RT(self, vec):
         self._check_batch()
         return self._op(_lib.OP_RT, vec)
+
+    def rt_stats(self, vec, qm, qS):
+        """(bsz, 3) rows (kn.qm, |kn|^2, kn^2.qS) of kn = _matmul_by_RT(vec), the three numbers
+        prediction takes from kn (`hipgp.py:436-443`), without the (bsz, M') tensor.  No autograd."""
+        self._check_batch()
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (vec, qm, qS, self.column)):
+            raise RuntimeError("rt_stats has no backward: call it under torch.no_grad() or on detached inputs")
+        return self._plan.rt_stats(vec, qm, qS)
 
     def _matmul_by_R(self, vec):
         self._check_batch()

@@ -74,6 +74,15 @@ int hgp_plan_set_column(hgp_plan* plan, const void* column, double jitter, doubl
  *  toeplitz_expanded.py:139-189).  x and y must not alias. */
 int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs);
 
+/* out3[n*3 + c] = (kn_n.qm, |kn_n|^2, kn_n^2.qS) for kn_n = R^T d_n, without writing kn
+ * (hipgp.py:436-443 as predict consumes toeplitz_tensor.py:85-97).  d: (nrhs, M); qm, qS: (M',);
+ * out3: 3*nrhs values; device, plan dtype; ordered on the plan's stream; fixed reduction order.
+ * 2-D / 3-D plans fuse the three sums into R^T's last pass (RHS-chunked as HGP_OP_RT); 1-D plans,
+ * the full-grid route and rows beyond one CU's LDS run R^T into plan scratch a bounded piece of
+ * RHS at a time.  nrhs = 0: nothing.  HGP_E_ARG: null plan / pointer, nrhs < 0; HGP_E_STATE: no
+ * column set. */
+int hgp_rt_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, const void* qS, void* out3);
+
 /* Batched PCG, exactly the recurrence of conj_grad2 (cg.py:44-80) for layout ROWS
  * (b,x:(nrhs,M)) and conj_grad (cg.py:5-41) for layout COLS (b,x:(M,nrhs)): A = K,
  * preconditioner C^-1 if use_precond, x0 = 0, per-RHS alpha/beta, stop when ALL
@@ -81,6 +90,8 @@ int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t n
  * by every later kernel), so the host is not synchronised per iteration (solves with
  * maxiter > 32 read the flag every 16 iterations to stop queueing no-op iterations).
  * iters_done (host, may be NULL): number of iterations executed (synchronises).
+ * x may be b itself (the solve in place of its right-hand side: b is read once, element by
+ * element, before x is first written), here and in hgp_pcg_begin.
  * Replaces ToeplitzTensor._solve (toeplitz_tensor.py:54-68) / InvMatmul.forward. */
 int hgp_pcg_solve(hgp_plan* plan, const void* b, void* x, int64_t nrhs, int maxiter,
                   double tol, int use_precond, int layout, int* iters_done);
