@@ -127,6 +127,9 @@ struct hgp_plan {
   DevBuf slab_part, slab_coef;
   // hgp_rt_stats: the fused epilogue's partials, and one piece of kn on the plans that materialise it
   DevBuf st_part, st_kn;
+  // hgp_rt_fit_stats: the lam accumulators of the side streams' RHS chunks, (streams - 1) M' values
+  // whatever nrhs (plans that materialise kn a piece at a time accumulate in lam itself)
+  DevBuf st_lam;
   int64_t cg_nrhs = 0;
   int cg_precond = 0, cg_layout = 0;
   void* cg_x_user = nullptr;
@@ -204,7 +207,7 @@ struct hgp_plan {
       bsPre[a].release(); bsPost[a].release(); bsFilt[a].release();
     }
     DevBuf* bufs[] = {&specK, &specI, &specR, &specRg, &specKg, &gridA, &gridB, &Dm3, &nclamp, &ws1, &ws2, &set1, &set2, &setM1, &setM2, &setC,
-                      &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn};
+                      &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn, &st_lam};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 3; ++i) {
       if (side[i]) (void)hipStreamDestroy(side[i]);
@@ -314,10 +317,15 @@ struct RowEpi {
 
 // Prediction statistics in place of R^T's output (hgp_rt_stats): the last pass runs EPI_STATS
 // against the shared M'-vectors qm / qs, and each RHS chunk's partials are finished into out3
+// With lam (hgp_rt_fit_stats) the last pass runs EPI_LAM instead, one launch per RHS: chunks of
+// stream slot 0 accumulate into lam itself, those of slot s > 0 into lam_side + (s - 1) M'
 struct RowStats {
   const void* qm;
   const void* qs;
   void* out3;
+  const void* iv = nullptr;
+  void* lam = nullptr;
+  void* lam_side = nullptr;
 };
 
 // the chunk (first RHS q0) view of an epilogue's in-kernel CG scalar
@@ -542,6 +550,22 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
       D.out.ptr = nullptr;                      // nothing is stored
       D.dot = nullptr; D.partial = nullptr;
       D.st_qm = stats->qm; D.st_qs = stats->qs; D.st_part = spc;
+      if (stats->lam != nullptr)
+        D.st_lam = slot == 0 ? reinterpret_cast<T*>(stats->lam)
+                             : reinterpret_cast<T*>(stats->lam_side) + (int64_t)(slot - 1) * g.out_M;
+    };
+    // EPI_LAM read-modify-writes lam without atomics: one launch per RHS (`lines` kernel lines
+    // each), so launches that touch the same lam positions are ordered by the chunk's stream
+    auto stats_lam = [&](PassDesc& D, int64_t lines, auto&& run_rowt) -> int {
+      for (int qi = 0; qi < qn; ++qi) {
+        PassDesc L = D;
+        L.Q = (int)lines;
+        L.in.ptr = reinterpret_cast<C2<T>*>(D.in.ptr) + (int64_t)qi * lines * D.in.q_stride;
+        L.st_part = spc + (int64_t)qi * rn_last * 3;
+        L.st_iv = reinterpret_cast<const T*>(stats->iv) + q0 + qi;
+        HGP_TRY(run_rowt(1, L, EPI_LAM));
+      }
+      return 0;
     };
     auto stats_finish = [&]() -> int {
       hipError_t e = rowdots_finish(P->dtype, spc, (int)rn_last, qn, reinterpret_cast<T*>(stats->out3) + q0 * 3, st);
@@ -665,7 +689,8 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
       }
       if (stats != nullptr) {
         stats_desc(Cd);
-        HGP_TRY(run_rowt(1, Cd, EPI_STATS));
+        if (stats->lam != nullptr) HGP_TRY(stats_lam(Cd, 1, run_rowt));
+        else HGP_TRY(run_rowt(1, Cd, EPI_STATS));
         HGP_TRY(stats_finish());
       } else if (pair == nullptr) {
         HGP_TRY(run_rowt(1, Cd, epi_mode));
@@ -765,7 +790,8 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
       if (stats != nullptr) {
         stats_desc(E);
         E.cg_div = (int)g.out[0];                 // qm / qS plane of kernel line q: q % out[0]
-        HGP_TRY(run_rowt(1, E, EPI_STATS));
+        if (stats->lam != nullptr) HGP_TRY(stats_lam(E, g.out[0], run_rowt));
+        else HGP_TRY(run_rowt(1, E, EPI_STATS));
         HGP_TRY(stats_finish());
       } else {
         HGP_TRY(run_rowt(1, E, epi_mode));
@@ -1553,6 +1579,50 @@ int rt_stats_t(hgp_plan* P, const void* dv, int64_t nrhs, const void* qm, const 
   return 0;
 }
 
+// hgp_rt_stats plus lam[j] = sum_n iv[n] kn_nj^2 (hipgp.py:241), kn never stored.  Fused plans run
+// R^T's sequence with the EPI_LAM row inverse last, one launch per RHS: a lam position has one
+// owner thread per launch, and the launches of a stream are ordered, so the plain read-modify-write
+// needs no atomics and the sum over the RHS has a fixed order.  The chunks of the plan's other
+// streams accumulate into their own M'-vectors (st_lam), added to lam in stream order after the
+// join.  The other plans (rt_stats_fused) reduce each bounded piece of kn by rows and by columns,
+// lam continuing from piece to piece.
+template <typename T>
+int rt_fit_stats_t(hgp_plan* P, const void* dv, int64_t nrhs, const void* qm, const void* qS, const void* iv,
+                   void* out3, void* lam) {
+  const size_t lam_b = (size_t)P->Mp * sizeof(T);
+  if (rt_stats_fused<T>(P)) {
+    const int NS = (int)std::min<int64_t>(std::max(1, P->nstreams), nrhs);   // run_op's stream count
+    HIP_TRY(hipMemsetAsync(lam, 0, lam_b, P->stream));
+    if (NS > 1) {
+      HGP_TRY(P->st_lam.ensure((size_t)(NS - 1) * lam_b));
+      HIP_TRY(hipMemsetAsync(P->st_lam.ptr, 0, (size_t)(NS - 1) * lam_b, P->stream));
+    }
+    RowStats st{qm, qS, out3};
+    st.iv = iv; st.lam = lam; st.lam_side = NS > 1 ? P->st_lam.ptr : nullptr;
+    HGP_TRY(run_op<T>(P, HGP_OP_RT, dv, nullptr, nrhs, nullptr, nullptr, nullptr, -1, nullptr, nullptr, nullptr,
+                      nullptr, &st));
+    for (int s = 1; s < NS; ++s) {
+      hipError_t e = vec_add(P->dtype, lam, reinterpret_cast<const T*>(P->st_lam.ptr) + (int64_t)(s - 1) * P->Mp, P->Mp,
+                             P->stream);
+      if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rt_fit_stats: ") + hipGetErrorString(e));
+    }
+    return 0;
+  }
+  const int64_t piece = std::max<int64_t>(1, std::min<int64_t>(nrhs, HGP_RT_STATS_PIECE / P->Mp));
+  HGP_TRY(P->st_kn.ensure((size_t)(piece * P->Mp) * sizeof(T)));
+  for (int64_t q0 = 0; q0 < nrhs; q0 += piece) {
+    const int64_t qn = std::min(piece, nrhs - q0);
+    HGP_TRY(run_op<T>(P, HGP_OP_RT, reinterpret_cast<const T*>(dv) + q0 * P->M, P->st_kn.ptr, qn, nullptr, nullptr,
+                      nullptr));
+    hipError_t e = meanfield_rowdots(P->dtype, P->st_kn.ptr, qn, P->Mp, qm, qS, reinterpret_cast<T*>(out3) + q0 * 3,
+                                     P->stream);
+    if (e == hipSuccess)
+      e = lam_cols(P->dtype, P->st_kn.ptr, qn, P->Mp, reinterpret_cast<const T*>(iv) + q0, lam, q0 > 0, P->stream);
+    if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rt_fit_stats: ") + hipGetErrorString(e));
+  }
+  return 0;
+}
+
 #define DISPATCH(P, FN, ...) ((P)->dtype == HGP_F64 ? FN<double>(__VA_ARGS__) : FN<float>(__VA_ARGS__))
 
 int check_plan(const hgp_plan* P) {
@@ -1781,6 +1851,22 @@ int hgp_rt_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, co
     return fail(HGP_E_ARG, "hgp_rt_stats: null d / qm / qS / out3");
   HGP_TRY(use_device(plan));
   return DISPATCH(plan, rt_stats_t, plan, d, nrhs, qm, qS, out3);
+}
+
+int hgp_rt_fit_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, const void* qS, const void* ivar,
+                     void* out3, void* lam) {
+  HGP_TRY(check_plan(plan));
+  if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  if (nrhs < 0) return fail(HGP_E_ARG, "hgp_rt_fit_stats: nrhs < 0");
+  if (lam == nullptr) return fail(HGP_E_ARG, "hgp_rt_fit_stats: null lam");
+  if (nrhs > 0 && (d == nullptr || qm == nullptr || qS == nullptr || ivar == nullptr || out3 == nullptr))
+    return fail(HGP_E_ARG, "hgp_rt_fit_stats: null d / qm / qS / ivar / out3");
+  HGP_TRY(use_device(plan));
+  if (nrhs == 0) {                                    // the empty sum
+    HIP_TRY(hipMemsetAsync(lam, 0, (size_t)plan->Mp * plan->esz, plan->stream));
+    return 0;
+  }
+  return DISPATCH(plan, rt_fit_stats_t, plan, d, nrhs, qm, qS, ivar, out3, lam);
 }
 
 int hgp_toeplitz_apply_pass(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs, int pass) {
@@ -2291,7 +2377,7 @@ int64_t plan_scratch_bytes(const hgp_plan* P) {
   const DevBuf* bufs[] = {&P->ws1, &P->ws2, &P->set1, &P->set2, &P->setM1, &P->setM2, &P->setC, &P->r, &P->z,
                           &P->p, &P->Ap, &P->part_op, &P->part_u, &P->part_f, &P->scal, &P->bT, &P->xT,
                           &P->gridA, &P->gridB,    // the full-grid R / R^T buffers (grid_r plans)
-                          &P->slab_part, &P->slab_coef, &P->st_part, &P->st_kn};
+                          &P->slab_part, &P->slab_coef, &P->st_part, &P->st_kn, &P->st_lam};
   int64_t b = 0;
   for (const DevBuf* d : bufs) b += (int64_t)d->bytes;
   return b;
@@ -2322,7 +2408,7 @@ int hgp_plan_trim(hgp_plan* plan) {
   DevBuf* bufs[] = {&plan->ws1, &plan->ws2, &plan->set1, &plan->set2, &plan->setM1, &plan->setM2, &plan->setC,
                     &plan->r, &plan->z, &plan->p, &plan->Ap, &plan->part_op, &plan->part_u, &plan->part_f,
                     &plan->scal, &plan->bT, &plan->xT, &plan->gridA, &plan->gridB, &plan->slab_part,
-                    &plan->slab_coef, &plan->st_part, &plan->st_kn};
+                    &plan->slab_coef, &plan->st_part, &plan->st_kn, &plan->st_lam};
   for (DevBuf* b : bufs) b->release();
   plan->drop_graph();                               // its kernels addressed the freed workspaces
   plan->last_apply = hgp_plan::ApplyKey();

@@ -93,6 +93,9 @@ hipError_t meanfield_stats(int dtype, const void* kn, int64_t nrhs, int64_t Mp, 
 hipError_t meanfield_rowdots(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* qm, const void* qS,
                              void* out3, hipStream_t s);
 hipError_t rowdots_finish(int dtype, const void* part, int np, int64_t nrhs, void* out3, hipStream_t s);
+hipError_t lam_cols(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* iv, void* lam, int cont,
+                    hipStream_t s);
+hipError_t vec_add(int dtype, void* dst, const void* src, int64_t n, hipStream_t s);
 hipError_t meanfield_cols(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* iv, const void* bdiff,
                           void* lam, void* dm, hipStream_t s);
 // expanded grid n[a] tiled by blocks of side b[a] (nb[a] per axis); bs points per block, nbw

@@ -164,9 +164,13 @@ enum { SPEC_REAL = 0, SPEC_CPLX = 1, SPEC_CPLX_CONJ = 2 };
 // C^-1 r that follows in the same PCG iteration) into the block's rows of the intermediate
 // EPI_STATS: nothing is stored; each row pair leaves the three prediction dots of its outputs y with
 // the shared M'-vectors qm / qS (sum y qm, sum y^2, sum y^2 qS; PassDesc::st_*)
-enum { EPI_OUT = 0, EPI_XR = 1, EPI_R = 2, EPI_XP = 3, EPI_RF = 4, EPI_STATS = 5 };
+// EPI_LAM: EPI_STATS, and lam[pos] += ivar[rhs] y^2 at every kept output position (the mean-field
+// natural-gradient sum over the minibatch, hipgp.py:241); a plain read-modify-write, so two RHS
+// must not be in one launch nor in flight on two streams against the same lam (PassDesc::st_lam)
+enum { EPI_OUT = 0, EPI_XR = 1, EPI_R = 2, EPI_XP = 3, EPI_RF = 4, EPI_STATS = 5, EPI_LAM = 6 };
 constexpr bool epi_r(int e) { return e == EPI_R || e == EPI_RF; }
-constexpr bool epi_cg(int e) { return e != EPI_OUT && e != EPI_STATS; }   // the fused PCG updates
+constexpr bool epi_st(int e) { return e == EPI_STATS || e == EPI_LAM; }   // the statistics epilogues
+constexpr bool epi_cg(int e) { return e != EPI_OUT && !epi_st(e); }       // the fused PCG updates
 
 struct View {
   void* ptr;
@@ -227,6 +231,11 @@ struct PassDesc {
   const void* st_qm;
   const void* st_qs;
   void* st_part;
+  // EPI_LAM: lam laid out as qm / qS (one RHS's output); st_iv[q] (3-D: st_iv[q / cg_div]) is the
+  // weight of kernel line q's RHS.  Each lam position has one owner thread per RHS and no atomics:
+  // the host launches one RHS at a time on a stream, and gives each stream its own lam
+  void* st_lam;
+  const void* st_iv;
 };
 
 constexpr int LDS_CAP = 160 * 1024;

@@ -170,6 +170,7 @@ static hipError_t launch_rowt_g(int inv, int epi, const PassDesc& d, hipStream_t
     if (epi == EPI_XP) return launch_rowt_inv<T, H, EPI_XP, G>(d, s);
     if (epi == EPI_RF) return launch_rowt_inv<T, H, EPI_RF, G>(d, s);
     if (epi == EPI_STATS) return launch_rowt_inv<T, H, EPI_STATS, G>(d, s);
+    if (epi == EPI_LAM) return launch_rowt_inv<T, H, EPI_LAM, G>(d, s);
     return launch_rowt_inv<T, H, EPI_OUT, G>(d, s);
   }
   const int64_t nb = (int64_t)d.Q * ((d.Rn + Cfg::C - 1) / Cfg::C);

@@ -737,17 +737,25 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
     }
     return;
   }
-  if constexpr (EPI == EPI_STATS) {
+  if constexpr (epi_st(EPI)) {
     // Prediction statistics: the pair's outputs y are formed as below and never stored; they leave
     // sum y qm, sum y^2 and sum y^2 qS (row a, then row b, per position) in partial [q][Rn][3].
     // qm / qS are one RHS's output layout shared by every RHS: the row's base takes no q (3-D: the
     // plane q % cg_div).  The three branches are EPI_OUT's below; the selects keep a cropped
     // position, an absent pair (its transform ran on pair 0's data) and an absent second row (its
     // imaginary part is rounding noise, not zero) out of the sums.
+    // EPI_LAM (the natural-gradient step, hipgp.py:234-250) also adds ivar[rhs] y^2 into lam at each
+    // kept position, lam addressed as qm / qS: a plain read-modify-write by the position's only
+    // owner in this launch (row pair -> one group, position -> one thread; 3-D: every line of a
+    // launch is another plane), its loads and stores cropped like the qm / qS loads, so a dropped
+    // position neither reads nor writes.  Launches that share a lam are ordered by the host.
+    constexpr bool LAM = EPI == EPI_LAM;
     const int64_t pl = d.cg_div > 1 ? (int64_t)(q % d.cg_div) * d.out.q_stride : 0;
     const int64_t ro = pl + (int64_t)(pvalid ? 2 * rp : 0) * d.out.r_stride;
     const T* qm_a = reinterpret_cast<const T*>(d.st_qm) + ro;
     const T* qs_a = reinterpret_cast<const T*>(d.st_qs) + ro;
+    T ivq = 0;
+    if constexpr (LAM) ivq = reinterpret_cast<const T*>(d.st_iv)[d.cg_div > 1 ? q / d.cg_div : q];
     T s0 = 0, s1 = 0, s2 = 0;
     auto acc = [&](T ya, T yb, T ma, T mb, T sa, T sb) {
       const T ya2 = ya * ya, yb2 = yb * yb;
@@ -762,6 +770,12 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
       const uint32_t rowb = (uint32_t)out_len * (uint32_t)sizeof(T);
       const BufRsrc ma = buf_rsrc(qm_a, pvalid ? rowb : 0u), mb = buf_rsrc(qm_a + d.out.r_stride, has2 ? rowb : 0u);
       const BufRsrc sa = buf_rsrc(qs_a, pvalid ? rowb : 0u), sb = buf_rsrc(qs_a + d.out.r_stride, has2 ? rowb : 0u);
+      BufRsrc la, lb2;
+      if constexpr (LAM) {
+        T* lam_a = reinterpret_cast<T*>(d.st_lam) + ro;
+        la = buf_rsrc(lam_a, pvalid ? rowb : 0u);
+        lb2 = buf_rsrc(lam_a + d.out.r_stride, has2 ? rowb : 0u);
+      }
       const uint32_t lo = (uint32_t)tt * (uint32_t)sizeof(T);
 #pragma unroll
       for (int k = 0; k < P; ++k) {
@@ -773,8 +787,13 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
             const C2<T> y = hh == 0 ? cadd<T>(va[k], wo) : csub<T>(va[k], wo);
             const uint32_t so = (uint32_t)(TT * k + hh * H) * (uint32_t)sizeof(T);
             const bool in = p + hh * H < out_len;
-            acc((in && pvalid) ? y.x : (T)0, (in && has2) ? y.y : (T)0, buf_ld<T>(ma, lo, so), buf_ld<T>(mb, lo, so),
-                buf_ld<T>(sa, lo, so), buf_ld<T>(sb, lo, so));
+            const T ya = (in && pvalid) ? y.x : (T)0, yb = (in && has2) ? y.y : (T)0;
+            acc(ya, yb, buf_ld<T>(ma, lo, so), buf_ld<T>(mb, lo, so), buf_ld<T>(sa, lo, so), buf_ld<T>(sb, lo, so));
+            if constexpr (LAM) {                // stores past a range are dropped
+              const T l0 = buf_ld<T>(la, lo, so), l1 = buf_ld<T>(lb2, lo, so);
+              buf_st<T>(l0 + ivq * (ya * ya), la, lo, so);
+              buf_st<T>(l1 + ivq * (yb * yb), lb2, lo, so);
+            }
           }
         }
       }
@@ -784,6 +803,8 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
       const int64_t bo = pl + (int64_t)(2 * rb * C) * d.out.r_stride;
       const BufRsrc rm = buf_rsrc(reinterpret_cast<const T*>(d.st_qm) + bo, 0x7fffffffu);
       const BufRsrc rs = buf_rsrc(reinterpret_cast<const T*>(d.st_qs) + bo, 0x7fffffffu);
+      BufRsrc rl;
+      if constexpr (LAM) rl = buf_rsrc(reinterpret_cast<T*>(d.st_lam) + bo, 0x7fffffffu);
       const uint32_t rowa = (uint32_t)(2 * l) * (uint32_t)d.out.r_stride, rowp = (uint32_t)d.out.r_stride;
       constexpr uint32_t DROP = 0x80000000u;
 #pragma unroll
@@ -798,8 +819,13 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
             const bool in = pvalid && pp < out_len;
             const uint32_t oa = in ? (rowa + (uint32_t)pp) * (uint32_t)sizeof(T) : DROP;
             const uint32_t ob = (in && has2) ? (rowa + rowp + (uint32_t)pp) * (uint32_t)sizeof(T) : DROP;
-            acc(in ? y.x : (T)0, (in && has2) ? y.y : (T)0, buf_ld<T>(rm, oa), buf_ld<T>(rm, ob), buf_ld<T>(rs, oa),
-                buf_ld<T>(rs, ob));
+            const T ya = in ? y.x : (T)0, yb = (in && has2) ? y.y : (T)0;
+            acc(ya, yb, buf_ld<T>(rm, oa), buf_ld<T>(rm, ob), buf_ld<T>(rs, oa), buf_ld<T>(rs, ob));
+            if constexpr (LAM) {
+              const T l0 = buf_ld<T>(rl, oa), l1 = buf_ld<T>(rl, ob);
+              buf_st<T>(l0 + ivq * (ya * ya), rl, oa);
+              buf_st<T>(l1 + ivq * (yb * yb), rl, ob);
+            }
           }
         }
       }
@@ -807,6 +833,8 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
       // plain branch (fp64 rows of several pairs per wave: reference-precision runs)
       const T* qm_b = qm_a + d.out.r_stride;
       const T* qs_b = qs_a + d.out.r_stride;
+      T* lam_a = LAM ? reinterpret_cast<T*>(d.st_lam) + ro : nullptr;
+      T* lam_b = LAM ? lam_a + d.out.r_stride : nullptr;
 #pragma unroll
       for (int k = 0; k < P; ++k) {
         const int p = tt + TT * k;
@@ -818,6 +846,10 @@ __global__ __launch_bounds__((RowTCfg<T, H, G, true>::THREADS), (RowTCfg<T, H, G
           if (pvalid && pp < out_len) {
             if (has2) acc(y.x, y.y, qm_a[pp], qm_b[pp], qs_a[pp], qs_b[pp]);
             else acc(y.x, (T)0, qm_a[pp], (T)0, qs_a[pp], (T)0);
+            if constexpr (LAM) {
+              lam_a[pp] = lam_a[pp] + ivq * (y.x * y.x);
+              if (has2) lam_b[pp] = lam_b[pp] + ivq * (y.y * y.y);
+            }
           }
         }
       }

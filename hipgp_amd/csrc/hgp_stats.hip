@@ -203,6 +203,66 @@ hipError_t meanfield_cols_t(const void* kn, int64_t nrhs, int64_t Mp, const void
   return hipGetLastError();
 }
 
+// lam_j = (cont ? lam_j : 0) + sum_n iv_n kn_nj^2 over one piece of kn, k_stats_cols's thread map and
+// order (hgp_rt_fit_stats on the plans that materialise kn a piece at a time)
+template <typename T>
+__global__ __launch_bounds__(ST_THREADS) void k_lam_cols(const T* __restrict__ kn, int64_t Mp, int nrhs,
+                                                        const T* __restrict__ iv, T* __restrict__ lam, int cont) {
+  constexpr int CPT = 4;
+  const int64_t j0 = (int64_t)blockIdx.x * ST_THREADS * CPT + threadIdx.x;
+  T l[CPT];
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+    const int64_t j = j0 + c * ST_THREADS;
+    l[c] = (cont && j < Mp) ? lam[j] : (T)0;
+  }
+  for (int b = 0; b < nrhs; ++b) {
+    const T ivb = iv[b];
+    const T* row = kn + (int64_t)b * Mp;
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+      const int64_t j = j0 + c * ST_THREADS;
+      if (j < Mp) {
+        const T v = row[j];
+        l[c] += ivb * (v * v);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+    const int64_t j = j0 + c * ST_THREADS;
+    if (j < Mp) lam[j] = l[c];
+  }
+}
+
+hipError_t lam_cols(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* iv, void* lam, int cont,
+                    hipStream_t s) {
+  if (Mp == 0) return hipSuccess;
+  const dim3 grid((unsigned)((Mp + ST_THREADS * 4 - 1) / (ST_THREADS * 4))), block(ST_THREADS);
+  if (dtype == HGP_F64)
+    hipLaunchKernelGGL((k_lam_cols<double>), grid, block, 0, s, (const double*)kn, Mp, (int)nrhs, (const double*)iv,
+                       (double*)lam, cont);
+  else
+    hipLaunchKernelGGL((k_lam_cols<float>), grid, block, 0, s, (const float*)kn, Mp, (int)nrhs, (const float*)iv,
+                       (float*)lam, cont);
+  return hipGetLastError();
+}
+
+// dst_j += src_j (the side streams' lam accumulators into lam, hgp_rt_fit_stats)
+template <typename T>
+__global__ __launch_bounds__(ST_THREADS) void k_vec_add(T* __restrict__ dst, const T* __restrict__ src, int64_t n) {
+  const int64_t j = (int64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+  if (j < n) dst[j] += src[j];
+}
+
+hipError_t vec_add(int dtype, void* dst, const void* src, int64_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const dim3 grid((unsigned)((n + ST_THREADS - 1) / ST_THREADS)), block(ST_THREADS);
+  if (dtype == HGP_F64) hipLaunchKernelGGL((k_vec_add<double>), grid, block, 0, s, (double*)dst, (const double*)src, n);
+  else hipLaunchKernelGGL((k_vec_add<float>), grid, block, 0, s, (float*)dst, (const float*)src, n);
+  return hipGetLastError();
+}
+
 hipError_t meanfield_rowdots(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* qm, const void* qS,
                              void* out3, hipStream_t s) {
   if (dtype == HGP_F64) return meanfield_rowdots_t<double>(kn, nrhs, Mp, qm, qS, out3, s);

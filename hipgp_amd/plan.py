@@ -201,6 +201,28 @@ class ToeplitzPlan:
             self._report_ws()
         return out
 
+    def rt_fit_stats(self, d, qm, qS, ivar):
+        """(out3 (B, 3), lam (M',)): out3 as `rt_stats`, lam[j] = sum_n ivar[n] kn_nj^2 of kn = R^T d,
+        without materialising the (B, M') kn (hgp_rt_fit_stats): d (B, M), qm / qS (M',) or (M', 1),
+        ivar (B,).  Deterministic."""
+        d = self._vec(d, "d", self.M)
+        vecs = []
+        for t, name, n in ((qm, "qm", self.Mprime), (qS, "qS", self.Mprime), (ivar, "ivar", d.shape[0])):
+            _lib.require_device_tensor(t, name)
+            if t.dtype != self.dtype or t.device != self.device:
+                raise TypeError(f"{name} is {t.dtype} on {t.device}, plan is {self.dtype} on {self.device}")
+            if t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} values, expected {n}")
+            vecs.append(t.detach().reshape(-1).contiguous())
+        out = torch.empty((d.shape[0], 3), dtype=self.dtype, device=self.device)
+        lam = torch.empty(self.Mprime, dtype=self.dtype, device=self.device)
+        self._bind_stream()
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        check(lib().hgp_rt_fit_stats(self._h, p(d), d.shape[0], p(vecs[0]), p(vecs[1]), p(vecs[2]), p(out), p(lam)))
+        if not _ws_warned:
+            self._report_ws()
+        return out, lam
+
     def column_grad(self, op, x, g):
         """d/dcolumn of sum(g * op(x)) through the operator's spectrum (hgp_plan_column_grad),
         (M,) in the plan dtype; x, g shaped like op's input / output (`toeplitz_tensor.py:20-125`)."""

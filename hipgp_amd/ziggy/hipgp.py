@@ -145,6 +145,11 @@ class ToeplitzInducingGP(SviGP):
         None where the family (or the whitening, or a caller's Kmm) has no fused route."""
         return None
 
+    def fit_stats(self, Knm, ybatch, Knn_diag, noise_std_batch=None, maxiter_cg=10, Kmm=None):
+        """The dict of `batch_stats` for `elbo_and_grad(fused=True)` without kn itself, or None
+        (Knm untouched) where the family, the whitening or a caller's Kmm has no fused route."""
+        return None
+
     def get_kl_to_prior(self, qm, qS):
         raise NotImplementedError
 
@@ -189,14 +194,25 @@ class ToeplitzInducingGP(SviGP):
 
     def elbo_and_grad(self, xbatch, ybatch, noise_std_batch=None, maxiter_cg=10, integrated_obs=False,
                       semi_integrated_estimator="analytic", semi_integrated_samps=10,
-                      print_debug_info=False, Kmm=None, mc_offset=None):
+                      print_debug_info=False, Kmm=None, mc_offset=None, fused=None):
         """ELBO estimate; sets theta1.grad / theta2.grad to minus the natural gradient
-        (`hipgp.py:194-276`).  mc_offset: see `SviGP._make_grams` (sharded fits)."""
+        (`hipgp.py:194-276`).  mc_offset: see `SviGP._make_grams` (sharded fits).
+
+        fused=True takes the batch sums straight from the R^T pass (`fit_stats`, hgp_rt_fit_stats)
+        where the family has them and no hyper-parameter gradient is asked for (the autograd ELBO
+        needs kn), so the (bsz, M') kn is never allocated; every other case takes the materialised
+        path.  None reads HGP_FIT_FUSED (default off)."""
         assert self.parameterization == 'expectation-family', \
             "need parameterization=expectation-family when performing natural gradient descent"
+        if fused is None:
+            fused = os.environ.get("HGP_FIT_FUSED", "0") not in ("", "0")
         Knm, Knn_diag = self._make_grams(xbatch, integrated_obs=integrated_obs,
                                          semi_integrated_estimator=semi_integrated_estimator,
                                          semi_integrated_samps=semi_integrated_samps, mc_offset=mc_offset)
+        if fused and not self.hyper_grad_needed(noise_std_batch):
+            stats = self.fit_stats(Knm, ybatch, Knn_diag, noise_std_batch, maxiter_cg=maxiter_cg, Kmm=Kmm)
+            if stats is not None:
+                return self.apply_stats(stats, xbatch.shape[0])
         kn = self.compute_kn(Knm, maxiter_cg=maxiter_cg, Kmm=Kmm)
         stats = self.batch_stats(kn, ybatch, Knn_diag, noise_std_batch)
         elbo = self.apply_stats(stats, xbatch.shape[0])
@@ -392,6 +408,54 @@ class MeanFieldToeplitzGP(ToeplitzInducingGP):
                 d0 = Kmm.inv_matmul(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
             qm, qS = self.standard_variational_params()
             return Kmm.rt_stats(d0, qm, qS)
+
+    def fit_stats(self, Knm, ybatch, Knn_diag, noise_std_batch=None, maxiter_cg=10, Kmm=None):
+        """`batch_stats` of kn = R^T K^-1 Knm^T (`hipgp.py:234-250`) without the (bsz, M') kn:
+        d = K^-1 Knm^T by compute_kn's PCG in place of Knm (consumed), the three row dots and
+        lam_sum from ToeplitzTensor.rt_fit_stats (hgp_rt_fit_stats) on d, a_n and bdiff_n from the
+        dots as in `batch_stats_slab`, and, R^T being linear,
+            dm_sum = -sum_n bdiff_n kn_n = R^T (-sum_n bdiff_n d_n):
+        one fixed-order (bsz, M) -> (M) column sum (hgp_meanfield_cols on d with Mp = M) and a
+        single-RHS R^T.  None, with Knm untouched, for cholesky whitening, an empty batch or a Kmm
+        without rt_fit_stats."""
+        if self.whitened_type != 'ziggy' or Knm.shape[0] == 0:
+            return None
+        if Kmm is None:
+            Kmm = self.toeplitz()
+        if not hasattr(Kmm, "rt_fit_stats"):
+            return None
+        with torch.no_grad():
+            Knm = Knm.detach()
+            B = Knm.shape[0]
+            dev, dt = Knm.device, Knm.dtype
+            if hasattr(Kmm, "inv_matmul_") and Knm.is_contiguous() and not Kmm.column.requires_grad:
+                d0 = Kmm.inv_matmul_(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
+            else:
+                d0 = Kmm.inv_matmul(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
+            qm, qS = self.standard_variational_params()
+            ivar, log_sd = self.noise_terms(noise_std_batch)
+            col = lambda v: torch.as_tensor(v, dtype=dt, device=dev).detach().reshape(-1).expand(B).contiguous()
+            y, iv, kd, lsd = col(ybatch), col(ivar), col(Knn_diag), col(log_sd)
+            qmv = qm.detach().reshape(-1).to(dt).contiguous()
+            qSv = qS.detach().reshape(-1).to(dt).contiguous()
+            dots, lam = Kmm.rt_fit_stats(d0, qmv, qSv, iv)
+            knm, knkn, knSkn = dots[:, 0], dots[:, 1], dots[:, 2]
+            an = -0.5 * iv * ((knm - y) ** 2 + kd - knkn + knSkn) - lsd - 0.5 * LN_2PI
+            bdiff = (iv * (knm - y)).contiguous()
+            if d0.is_cuda:
+                import ctypes
+                from hipgp_amd import _lib
+                p = lambda t: ctypes.c_void_p(t.data_ptr())
+                d0 = d0.contiguous()
+                M = d0.shape[1]
+                scr = torch.empty(M, dtype=dt, device=dev)      # sum_n iv_n d_nj^2: not used
+                v = torch.empty(M, dtype=dt, device=dev)
+                _lib.check(_lib.lib().hgp_meanfield_cols(_lib.dtype_code(dt), p(d0), B, M, p(iv), p(bdiff), p(scr),
+                                                         p(v), _lib.stream_ptr(dev)))
+            else:       # CPU tensors only in the host-logic tests
+                v = -(bdiff[None, :].matmul(d0)).reshape(-1)
+            dm = Kmm._matmul_by_RT(v[None, :]).reshape(-1)
+        return {"an_sum": an.sum(), "lam_sum": lam.reshape(-1), "dm_sum": dm, "n": B}
 
     # ---- natural gradient as batch sums + update (sharding-friendly) ------------------------
     def batch_stats(self, kn, ybatch, Knn_diag, noise_std_batch=None):

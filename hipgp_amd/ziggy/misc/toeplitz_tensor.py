@@ -6,6 +6,7 @@ Operator map (reference line -> here):
   _matmul_by_K     (:70-83)             -> HGP_OP_K
   _matmul_by_RT    (:85-97)             -> HGP_OP_RT
   rt_stats (no reference line)          -> hgp_rt_stats (R^T with predict's three dots fused in)
+  rt_fit_stats (no reference line)      -> hgp_rt_fit_stats (those dots and the lam column sums)
   _matmul_by_R     (:99-112)            -> HGP_OP_R
   _matmul_by_Cinv  (:114-125)           -> HGP_OP_CINV
   _solve / conj_grad2 (:54-68)          -> hgp_pcg_solve (device-side early-exit flag)
@@ -113,6 +114,15 @@ class ToeplitzTensor:
         if torch.is_grad_enabled() and any(t.requires_grad for t in (vec, qm, qS, self.column)):
             raise RuntimeError("rt_stats has no backward: call it under torch.no_grad() or on detached inputs")
         return self._plan.rt_stats(vec, qm, qS)
+
+    def rt_fit_stats(self, vec, qm, qS, ivar):
+        """(out3 (bsz, 3), lam (M',)): `rt_stats`, and lam[j] = sum_n ivar[n] kn_nj^2, the sums the
+        mean-field natural-gradient step takes from kn (`hipgp.py:234-250`), without the (bsz, M')
+        tensor (hgp_rt_fit_stats).  No autograd."""
+        self._check_batch()
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (vec, qm, qS, ivar, self.column)):
+            raise RuntimeError("rt_fit_stats has no backward: call it under torch.no_grad() or on detached inputs")
+        return self._plan.rt_fit_stats(vec, qm, qS, ivar)
 
     def _matmul_by_R(self, vec):
         self._check_batch()

@@ -83,6 +83,21 @@ int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t n
  * column set. */
 int hgp_rt_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, const void* qS, void* out3);
 
+/* The mean-field natural-gradient step's sums (hipgp.py:234-250) without writing kn = R^T d:
+ * out3 as hgp_rt_stats, and lam[j] = sum_n ivar[n] kn_nj^2 (hipgp.py:241; M' values, overwritten).
+ * ivar: nrhs values; the rest as hgp_rt_stats.  No atomics, fixed order: bit-reproducible for a
+ * given plan and nrhs.  2-D / 3-D plans fuse both into R^T's last pass (RHS-chunked as HGP_OP_RT,
+ * one row-inverse launch per RHS so that the lam updates of two RHS are ordered; the RHS chunks of
+ * the plan's other streams accumulate into M'-vectors of plan scratch, added in stream order at
+ * the end); 1-D plans, the full-grid route and rows beyond one CU's LDS run R^T into plan scratch
+ * a bounded piece of RHS at a time and reduce each piece by rows and by columns.  Extra memory
+ * O(M') (fused) or one piece (otherwise), independent of nrhs; see hgp_plan_mem.
+ * nrhs = 0: lam zeroed.  HGP_E_ARG: null plan / pointer, nrhs < 0; HGP_E_STATE: no column set.
+ * dm = -sum_n bdiff_n kn_n needs no kn either: R^T is linear, so it is one single-RHS
+ * HGP_OP_RT of -sum_n bdiff_n d_n (hgp_meanfield_cols on d with Mp = M). */
+int hgp_rt_fit_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, const void* qS,
+                     const void* ivar, void* out3, void* lam);
+
 /* Batched PCG, exactly the recurrence of conj_grad2 (cg.py:44-80) for layout ROWS
  * (b,x:(nrhs,M)) and conj_grad (cg.py:5-41) for layout COLS (b,x:(M,nrhs)): A = K,
  * preconditioner C^-1 if use_precond, x0 = 0, per-RHS alpha/beta, stop when ALL
