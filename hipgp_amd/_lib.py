@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("HGP_LIB") or os.path.join(_HERE, "libhipgp.so")
 
 HGP_F32, HGP_F64 = 0, 1
 OP_K, OP_CINV, OP_RT, OP_R = 0, 1, 2, 3
+OP_RSQ = 4   # (R o R) w, hgp_toeplitz_apply only (include/hipgp.h)
 SPEC_D, SPEC_DSQRT, SPEC_DI = 0, 1, 2
 LAYOUT_ROWS, LAYOUT_COLS = 0, 1
 SLAB_FWD, SLAB_CONV, SLAB_INV, SLAB_CONV_A2A = 0, 1, 2, 3

@@ -117,6 +117,11 @@ struct hgp_plan {
   // real parts, C^-1 in the imaginary parts of specKg
   bool grid_k = false;
   DevBuf specRg, specKg, gridA, gridB;
+  // HGP_OP_RSQ's spectrum: the squared generator s^2 in specR's layout, scale and real / complex
+  // choice.  Built on the op's first use after a set_column (ensure_rsq_t), released by the next
+  // set_column; a table (hgp_plan_mem) that hgp_plan_trim keeps
+  DevBuf specR2;
+  bool have_spec2 = false;
   double clamp_min = 1e-6;                // of the last set_column (the clamp's gradient mask)
   DevBuf nclamp;
   // scratch
@@ -175,7 +180,7 @@ struct hgp_plan {
     // every plan-owned buffer an op's launches address (workspaces, the full-grid route's
     // buffers, the spectra): a reallocation of any of them -- e.g. R^T on a grid_k plan growing
     // gridA / gridB past K's size -- must invalidate a captured graph
-    static constexpr int NB = 9;
+    static constexpr int NB = 10;
     const void* buf[NB] = {};
     bool operator==(const ApplyKey& o) const {
       if (!(op == o.op && x == o.x && y == o.y && nrhs == o.nrhs && stream == o.stream)) return false;
@@ -185,7 +190,8 @@ struct hgp_plan {
     }
   };
   void key_buffers(ApplyKey& k) const {
-    const DevBuf* b[ApplyKey::NB] = {&ws1, &ws2, &gridA, &gridB, &specK, &specI, &specR, &specRg, &specKg};
+    const DevBuf* b[ApplyKey::NB] = {&ws1, &ws2, &gridA, &gridB, &specK, &specI, &specR, &specRg, &specKg,
+                                     &specR2};
     for (int i = 0; i < ApplyKey::NB; ++i) k.buf[i] = b[i]->ptr;
   }
   ApplyKey last_apply, graph_key;
@@ -206,7 +212,7 @@ struct hgp_plan {
       for (int j = 0; j < NLEV; ++j) { tw64Kl[a][j].release(); tw64Rl[a][j].release(); }
       bsPre[a].release(); bsPost[a].release(); bsFilt[a].release();
     }
-    DevBuf* bufs[] = {&specK, &specI, &specR, &specRg, &specKg, &gridA, &gridB, &Dm3, &nclamp, &ws1, &ws2, &set1, &set2, &setM1, &setM2, &setC,
+    DevBuf* bufs[] = {&specK, &specI, &specR, &specR2, &specRg, &specKg, &gridA, &gridB, &Dm3, &nclamp, &ws1, &ws2, &set1, &set2, &setM1, &setM2, &setC,
                       &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn, &st_lam};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 3; ++i) {
@@ -237,23 +243,29 @@ struct OpGeom {
   int spec_kind;
 };
 
+// R-type ops run on the L_R grid: R^T, R and HGP_OP_RSQ, which is R in everything but its spectrum
+bool r_type(int op) { return op == HGP_OP_RT || op == HGP_OP_R || op == HGP_OP_RSQ; }
+
 OpGeom op_geom(const hgp_plan* P, int op) {
   OpGeom g;
   for (int a = 0; a < 3; ++a) { g.in[a] = 1; g.out[a] = 1; g.L[a] = 1; }
   g.in_M = g.out_M = 1;
+  const bool n_in = op == HGP_OP_R || op == HGP_OP_RSQ;   // input on the n-grid
   for (int a = 0; a < P->d; ++a) {
-    const bool rtype = (op == HGP_OP_RT || op == HGP_OP_R);
-    g.L[a] = rtype ? P->LR[a] : P->LK[a];
-    g.in[a] = (op == HGP_OP_R) ? P->n[a] : P->m[a];
+    g.L[a] = r_type(op) ? P->LR[a] : P->LK[a];
+    g.in[a] = n_in ? P->n[a] : P->m[a];
     g.out[a] = (op == HGP_OP_RT) ? P->n[a] : P->m[a];
     g.in_M *= g.in[a];
     g.out_M *= g.out[a];
   }
-  g.tw = (op == HGP_OP_RT || op == HGP_OP_R) ? P->twR : P->twK;
+  g.tw = r_type(op) ? P->twR : P->twK;
   if (op == HGP_OP_K) { g.spec = P->specK.ptr; g.spec_kind = SPEC_REAL; }
   else if (op == HGP_OP_CINV) { g.spec = P->specI.ptr; g.spec_kind = SPEC_REAL; }
   else if (op == HGP_OP_RT) { g.spec = P->specR.ptr; g.spec_kind = P->r_real ? SPEC_REAL : SPEC_CPLX; }
-  else { g.spec = P->specR.ptr; g.spec_kind = P->r_real ? SPEC_REAL : SPEC_CPLX_CONJ; }
+  else {
+    g.spec = op == HGP_OP_RSQ ? P->specR2.ptr : P->specR.ptr;
+    g.spec_kind = P->r_real ? SPEC_REAL : SPEC_CPLX_CONJ;
+  }
   return g;
 }
 
@@ -415,7 +427,7 @@ int run_op_grid(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const
 }
 
 bool grid_route(const hgp_plan* P, int op) {
-  return (op == HGP_OP_R || op == HGP_OP_RT) ? P->grid_r : P->grid_k;
+  return r_type(op) ? P->grid_r : P->grid_k;
 }
 
 // whether R^T of this plan ends in the row-inverse kernel (the 2-D / 3-D row-pair sequences of
@@ -433,6 +445,7 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
            const int* done, int only_pass = -1, void* spart = nullptr, const RowEpi* epi = nullptr,
            const MidFn* mid = nullptr, const PairOp* pair = nullptr, const RowStats* stats = nullptr) {
   if (grid_route(P, op)) {
+    if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "internal: HGP_OP_RSQ has no full-grid route");
     if (spart != nullptr || epi != nullptr || mid != nullptr || only_pass >= 0 || stats != nullptr)
       return fail(HGP_E_UNSUPPORTED, "internal: the full-grid route has no fused PCG epilogue or pass split");
     // after the break (`done` set) every transform / embed / crop kernel of the route is a device
@@ -1046,6 +1059,113 @@ int dct_axis(hgp_plan* P, int ax, const double* in, double* out, int nb, double 
   return 0;
 }
 
+// whether the plan's R-type pass spectra are real: d >= 2, no L_R axis beyond the fp64 base pass,
+// L_R >= 2n - 1 on every axis (the filter then embeds evenly), and not the full-grid route
+bool r_long(const hgp_plan* P) {
+  bool long_r = false;
+  for (int ax = 0; ax < P->d; ++ax) long_r = long_r || P->LR[ax] / 2 > 8192;
+  return long_r;
+}
+bool r_spectrum_real(const hgp_plan* P) {
+  bool sym = P->d >= 2 && !r_long(P) && !P->grid_r;
+  for (int ax = 0; ax < P->d; ++ax) sym = sym && P->LR[ax] >= 2 * P->n[ax] - 1;
+  return sym;
+}
+
+// set-up grids of the R-type spectra (complex fp64 values): the compact R grid of
+// fwd_grid_real_f64 has a last axis of compact_stride(L) >= L/2 + 1 columns, more than L itself
+// when L = 4 (an axis of 2 points)
+int64_t r_setup_grid(const hgp_plan* P) {
+  const int64_t Lr_last = P->LR[P->d - 1];
+  return std::max(P->prodLR, P->prodLR / Lr_last * compact_stride(Lr_last));
+}
+
+// Generator on the m-grid -> R-type pass spectrum.  gv: the unique values of an even, n-periodic
+// generator (s = IFFT_n(sqrt D) for R / R^T, s^2 for HGP_OP_RSQ); embedded on the L_R grid,
+// transformed in fp64 and extracted into `spec` in the layout the op's axis-0 pass reads, scaled
+// by 1 / prod L_R; real where P->r_real, else complex.  grid_r plans: the complex transform in its
+// stored order (spec = specRg).  g1, g2: set-up grids of r_setup_grid(P) values.
+template <typename T>
+int r_spectrum(hgp_plan* P, const double* gv, DevBuf& spec, double2* g1, double2* g2) {
+  hipStream_t s = P->stream;
+  const int d = P->d;
+  GridDims gd;
+  gd.d = d;
+  for (int ax = 0; ax < 3; ++ax) { gd.m[ax] = P->m[ax]; gd.n[ax] = P->n[ax]; gd.L[ax] = P->LR[ax]; }
+  const int compact = d > 1 ? 1 : 0;
+  const int64_t LRl = P->LR[d - 1];
+  const int64_t SR = compact ? compact_stride(LRl) : LRl;
+  // 3-D: [c2][k1][k0] (c2 <= H2, no pitch padding), the contiguous axis-0 lines (q, c2, k1)
+  const int64_t nR = d == 3 ? P->prodLR / LRl * (LRl / 2 + 1) : P->prodLR / LRl * SR;
+  const bool sym = P->r_real;
+  double2* F = nullptr;
+  if (P->grid_r) {
+    // R / R^T on the full grid only (run_op_grid): the complex transform in its stored order, / N
+    embed_R(gv, g1, gd, s);
+    HGP_TRY(fwd_grid_f64(P, P->LR, P->tw64R, g1, g2, &F));
+    HGP_TRY(spec.ensure((size_t)P->prodLR * sizeof(double2)));
+    scale_copy(F, reinterpret_cast<double2*>(spec.ptr), P->prodLR, 1.0 / (double)P->prodLR, s);
+  } else if (d == 1) {
+    HGP_TRY(spec.ensure((size_t)nR * sizeof(C2<T>)));
+    embed_R(gv, g1, gd, s);
+    HGP_TRY(fwd_grid_f64(P, P->LR, P->tw64R, g1, g2, &F));
+    extract_cplx<T>(F, spec.ptr, nR, LRl, SR, compact, 1.0 / (double)P->prodLR, s);
+  } else if (!r_long(P)) {
+    HGP_TRY(spec.ensure((size_t)nR * (sym ? sizeof(T) : sizeof(C2<T>))));
+    // the R filter is real: real row-pair transform of the last axis, compact columns only after
+    embed_R_real(gv, reinterpret_cast<double*>(g1), gd, sym ? 1 : 0, s);
+    HGP_TRY(fwd_grid_real_f64(P, P->LR, P->tw64R, reinterpret_cast<const double*>(g1), g2, SR));
+    if (sym)   // even filter: its spectrum is real (the imaginary parts are rounding noise)
+      extract_t_re<T>(g2, spec.ptr, P->LR[0], d == 3 ? P->LR[1] : 1, LRl / 2, SR, 1,
+                      1.0 / (double)P->prodLR, s);
+    else
+      extract_t<T>(g2, spec.ptr, nullptr, P->LR[0], d == 3 ? P->LR[1] : 1, LRl / 2, SR, 1,
+                   1.0 / (double)P->prodLR, s);
+  } else {
+    // an axis of L_R > 16384 points (fp32 passes of 16384-point halves): the full complex grid
+    // through fft_lines_f64's radix-2 step
+    HGP_TRY(spec.ensure((size_t)nR * sizeof(C2<T>)));
+    embed_R(gv, g1, gd, s);
+    HGP_TRY(fwd_grid_f64(P, P->LR, P->tw64R, g1, g2, &F));
+    extract_t<T>(F, spec.ptr, nullptr, P->LR[0], d == 3 ? P->LR[1] : 1, LRl / 2, LRl, 0,
+                 1.0 / (double)P->prodLR, s);
+  }
+  return 0;
+}
+
+// HGP_OP_RSQ's spectrum, on the op's first use after a set_column: s = IDCT(sqrt D) on the m-grid
+// again (sqrt D is still in Dm3, which hgp_get_spectrum serves), squared elementwise in fp64, then
+// the same generator -> spectrum step as specR.  The set-up scratch may have been trimmed since
+// set_column: re-ensured here.  s^2 is even and n-periodic like s, so the L_R >= n + m - 1 window
+// argument holds unchanged and the operator is exact.
+template <typename T>
+int ensure_rsq_t(hgp_plan* P) {
+  if (P->have_spec2) return 0;
+  if (P->grid_r) return fail(HGP_E_UNSUPPORTED, "internal: HGP_OP_RSQ has no full-grid route");
+  hipStream_t s = P->stream;
+  const int d = P->d;
+  const int64_t M = P->M;
+  HGP_TRY(P->setM1.ensure((size_t)M * sizeof(double)));
+  HGP_TRY(P->setM2.ensure((size_t)M * sizeof(double)));
+  const int64_t big = r_setup_grid(P);
+  HGP_TRY(P->set1.ensure((size_t)big * sizeof(double2)));
+  HGP_TRY(P->set2.ensure((size_t)big * sizeof(double2)));
+  const double* src = reinterpret_cast<const double*>(P->Dm3.ptr) + 2 * M;   // Dm3 = [D | 1/D | sqrt D]
+  double* dst = reinterpret_cast<double*>(P->setM1.ptr);
+  double* oth = reinterpret_cast<double*>(P->setM2.ptr);
+  for (int ax = 0; ax < d; ++ax) {
+    HGP_TRY(dct_axis(P, ax, src, dst, 1, 1.0 / (double)P->n[ax]));
+    src = dst;
+    std::swap(dst, oth);
+  }
+  square_f64(src, oth, M, s);   // oth: the buffer the last axis wrote, squared in place
+  HGP_TRY(r_spectrum<T>(P, oth, P->specR2, reinterpret_cast<double2*>(P->set1.ptr),
+                        reinterpret_cast<double2*>(P->set2.ptr)));
+  HIP_TRY(hipGetLastError());
+  P->have_spec2 = true;
+  return 0;
+}
+
 template <typename T>
 int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_min, int64_t* n_clamped) {
   hipStream_t s = P->stream;
@@ -1082,10 +1202,7 @@ int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_mi
   const double* cI = src + M;
   const double* sv = src + 2 * M;
   // operator spectra on the power-of-two grids
-  // the compact R grid of fwd_grid_real_f64 has a last axis of compact_stride(L) >= L/2 + 1
-  // columns, more than L itself when L = 4 (an axis of 2 points)
-  const int64_t Lr_last = P->LR[d - 1];
-  const int64_t big = std::max({P->prodLK, P->prodLR, P->prodLR / Lr_last * compact_stride(Lr_last)});
+  const int64_t big = std::max(P->prodLK, r_setup_grid(P));
   HGP_TRY(P->set1.ensure((size_t)big * sizeof(double2)));
   HGP_TRY(P->set2.ensure((size_t)big * sizeof(double2)));
   double2* g1 = reinterpret_cast<double2*>(P->set1.ptr);
@@ -1104,11 +1221,10 @@ int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_mi
     scale_copy(F, reinterpret_cast<double2*>(P->specKg.ptr), P->prodLK, 1.0 / (double)P->prodLK, s, pmx);
   }
   const int compact = d > 1 ? 1 : 0;
-  const int64_t LKl = P->LK[d - 1], LRl = P->LR[d - 1];
-  const int64_t SK = compact ? compact_stride(LKl) : LKl, SR = compact ? compact_stride(LRl) : LRl;
+  const int64_t LKl = P->LK[d - 1];
+  const int64_t SK = compact ? compact_stride(LKl) : LKl;
   // 3-D: [c2][k1][k0] (c2 <= H2, no pitch padding), the contiguous axis-0 lines (q, c2, k1)
   const int64_t nK = d == 3 ? P->prodLK / LKl * (LKl / 2 + 1) : P->prodLK / LKl * SK;
-  const int64_t nR = d == 3 ? P->prodLR / LRl * (LRl / 2 + 1) : P->prodLR / LRl * SR;
   if (!P->grid_k) {   // the pass spectra (grid_k plans run K / C^-1 on the full grid)
     HGP_TRY(P->specK.ensure((size_t)nK * sizeof(T)));
     HGP_TRY(P->specI.ensure((size_t)nK * sizeof(T)));
@@ -1119,43 +1235,11 @@ int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_mi
       extract_t<T>(F, P->specK.ptr, P->specI.ptr, P->LK[0], d == 3 ? P->LK[1] : 1, LKl / 2, LKl, 0,
                    1.0 / (double)P->prodLK, s, pmx);
   }
-  for (int ax = 0; ax < 3; ++ax) gd.L[ax] = P->LR[ax];
-  bool long_r = false;
-  for (int ax = 0; ax < d; ++ax) long_r = long_r || P->LR[ax] / 2 > 8192;
-  bool sym = d >= 2 && !long_r;
-  for (int ax = 0; ax < d; ++ax) sym = sym && P->LR[ax] >= 2 * P->n[ax] - 1;
-  P->r_real = sym && !P->grid_r;
-  if (P->grid_r) {
-    // R / R^T on the full grid only (run_op_grid): the complex transform in its stored order, / N
-    embed_R(sv, g1, gd, s);
-    HGP_TRY(fwd_grid_f64(P, P->LR, P->tw64R, g1, g2, &F));
-    HGP_TRY(P->specRg.ensure((size_t)P->prodLR * sizeof(double2)));
-    scale_copy(F, reinterpret_cast<double2*>(P->specRg.ptr), P->prodLR, 1.0 / (double)P->prodLR, s);
-  } else if (d == 1) {
-    HGP_TRY(P->specR.ensure((size_t)nR * sizeof(C2<T>)));
-    embed_R(sv, g1, gd, s);
-    HGP_TRY(fwd_grid_f64(P, P->LR, P->tw64R, g1, g2, &F));
-    extract_cplx<T>(F, P->specR.ptr, nR, LRl, SR, compact, 1.0 / (double)P->prodLR, s);
-  } else if (!long_r) {
-    HGP_TRY(P->specR.ensure((size_t)nR * (sym ? sizeof(T) : sizeof(C2<T>))));
-    // the R filter is real: real row-pair transform of the last axis, compact columns only after
-    embed_R_real(sv, reinterpret_cast<double*>(g1), gd, sym ? 1 : 0, s);
-    HGP_TRY(fwd_grid_real_f64(P, P->LR, P->tw64R, reinterpret_cast<const double*>(g1), g2, SR));
-    if (sym)   // even filter: its spectrum is real (the imaginary parts are rounding noise)
-      extract_t_re<T>(g2, P->specR.ptr, P->LR[0], d == 3 ? P->LR[1] : 1, LRl / 2, SR, 1,
-                      1.0 / (double)P->prodLR, s);
-    else
-      extract_t<T>(g2, P->specR.ptr, nullptr, P->LR[0], d == 3 ? P->LR[1] : 1, LRl / 2, SR, 1,
-                   1.0 / (double)P->prodLR, s);
-  } else {
-    // an axis of L_R > 16384 points (fp32 passes of 16384-point halves): the full complex grid
-    // through fft_lines_f64's radix-2 step
-    HGP_TRY(P->specR.ensure((size_t)nR * sizeof(C2<T>)));
-    embed_R(sv, g1, gd, s);
-    HGP_TRY(fwd_grid_f64(P, P->LR, P->tw64R, g1, g2, &F));
-    extract_t<T>(F, P->specR.ptr, nullptr, P->LR[0], d == 3 ? P->LR[1] : 1, LRl / 2, LRl, 0,
-                 1.0 / (double)P->prodLR, s);
-  }
+  P->r_real = r_spectrum_real(P);
+  // a new column: HGP_OP_RSQ's table of the previous one goes, and is rebuilt when next asked for
+  P->specR2.release();
+  P->have_spec2 = false;
+  HGP_TRY(r_spectrum<T>(P, sv, P->grid_r ? P->specRg : P->specR, g1, g2));
   HIP_TRY(hipGetLastError());
   P->have_spec = true;
   if (n_clamped) {
@@ -1781,18 +1865,28 @@ int hgp_plan_set_column(hgp_plan* plan, const void* column, double jitter, doubl
 int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs) {
   HGP_TRY(check_plan(plan));
   if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
-  if (op < HGP_OP_K || op > HGP_OP_R) return fail(HGP_E_ARG, "bad op");
+  if (op < HGP_OP_K || op > HGP_OP_RSQ) return fail(HGP_E_ARG, "bad op");
   if (nrhs < 0 || (nrhs > 0 && (x == nullptr || y == nullptr))) return fail(HGP_E_ARG, "bad x/y/nrhs");
   if (x == y) return fail(HGP_E_ARG, "x and y must not alias");
+  if (op == HGP_OP_RSQ && plan->grid_r)
+    return fail(HGP_E_UNSUPPORTED, "HGP_OP_RSQ on the full-grid route (grid_r: fp64 R / R^T lines of more than 16384 "
+                                   "points, or an axis of more than 8192 points) is not supported");
   if (nrhs == 0) return 0;
   HGP_TRY(use_device(plan));
   hgp_plan* P = plan;
-  hgp_plan::ApplyKey key;
-  key.op = op; key.x = x; key.y = y; key.nrhs = nrhs; key.stream = P->stream;
-  P->key_buffers(key);
   // a caller that is itself capturing (e.g. torch.cuda.graphs) records our launches directly
   hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(P->stream, &cst) != hipSuccess) { (void)hipGetLastError(); cst = hipStreamCaptureStatusActive; }
+  if (op == HGP_OP_RSQ && !P->have_spec2) {
+    // the squared-generator spectrum is built on first use: it allocates and may synchronise
+    if (cst != hipStreamCaptureStatusNone)
+      return fail(HGP_E_STATE, "the first HGP_OP_RSQ after hgp_plan_set_column builds its spectrum and must not "
+                               "run inside a stream capture");
+    HGP_TRY(DISPATCH(plan, ensure_rsq_t, plan));
+  }
+  hgp_plan::ApplyKey key;
+  key.op = op; key.x = x; key.y = y; key.nrhs = nrhs; key.stream = P->stream;
+  P->key_buffers(key);
   if (!P->use_graphs || P->d < 2 || cst != hipStreamCaptureStatusNone)
     return DISPATCH(plan, run_op, plan, op, x, y, nrhs, nullptr, nullptr, nullptr);
   if (P->graph_exec != nullptr && key == P->graph_key) {
@@ -1872,6 +1966,7 @@ int hgp_rt_fit_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm
 int hgp_toeplitz_apply_pass(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs, int pass) {
   HGP_TRY(check_plan(plan));
   if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "HGP_OP_RSQ has no pass split (hgp_toeplitz_apply only)");
   if (op < HGP_OP_K || op > HGP_OP_R || pass < -1) return fail(HGP_E_ARG, "bad op/pass");
   if (nrhs <= 0 || x == nullptr || y == nullptr || x == y) return fail(HGP_E_ARG, "bad x/y/nrhs");
   HGP_TRY(use_device(plan));
@@ -2197,6 +2292,7 @@ int xcorr_grid(hgp_plan* P, int useR, const void* v, const void* h, int h_period
 int hgp_plan_column_grad(hgp_plan* plan, int op, const void* x, const void* g, int64_t nrhs, void* column_grad) {
   HGP_TRY(check_plan(plan));
   if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "HGP_OP_RSQ has no column gradient");
   if (op < HGP_OP_K || op > HGP_OP_R) return fail(HGP_E_ARG, "bad op");
   if (nrhs < 0 || column_grad == nullptr || (nrhs > 0 && (x == nullptr || g == nullptr)))
     return fail(HGP_E_ARG, "bad nrhs or null pointer");
@@ -2263,6 +2359,7 @@ int hgp_plan_dqf(hgp_plan* plan, const void* left, const void* right, int64_t nv
 
 int hgp_slab_info(const hgp_plan* plan, int op, int64_t* ngroups, int64_t* inner) {
   HGP_TRY(check_plan(plan));
+  if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "HGP_OP_RSQ has no grid-block (slab) split");
   if (op < HGP_OP_K || op > HGP_OP_R) return fail(HGP_E_ARG, "bad op");
   if (plan->d < 2) return fail(HGP_E_UNSUPPORTED, "slab sharding needs a 2-D or 3-D grid");
   const SlabGeom g = slab_geom(plan, op);
@@ -2275,6 +2372,7 @@ int hgp_slab_pass_ex(hgp_plan* plan, int op, int stage, const void* in, void* ou
                      int64_t g0, int64_t ng, const void* dotv, void* dot_out, const int* done) {
   HGP_TRY(check_plan(plan));
   if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "HGP_OP_RSQ has no grid-block (slab) split");
   if (op < HGP_OP_K || op > HGP_OP_R) return fail(HGP_E_ARG, "bad op");
   if (plan->d < 2) return fail(HGP_E_UNSUPPORTED, "slab sharding needs a 2-D or 3-D grid");
   if (stage < HGP_SLAB_FWD || stage > HGP_SLAB_CONV_A2A) return fail(HGP_E_ARG, "bad slab stage");
@@ -2392,7 +2490,7 @@ int hgp_plan_mem(const hgp_plan* plan, int64_t* scratch_bytes, int64_t* table_by
       b += (int64_t)(plan->twK[a].bytes + plan->twR[a].bytes + plan->tw64K[a].bytes + plan->tw64R[a].bytes +
                      plan->bsPre[a].bytes + plan->bsPost[a].bytes + plan->bsFilt[a].bytes);
     b += (int64_t)(plan->specK.bytes + plan->specI.bytes + plan->specR.bytes + plan->specRg.bytes + plan->specKg.bytes +
-                   plan->Dm3.bytes);
+                   plan->Dm3.bytes + plan->specR2.bytes);
     *table_bytes = b;
   }
   return 0;

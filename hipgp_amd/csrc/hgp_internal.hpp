@@ -39,6 +39,7 @@ void chirp_pre(const double* x, const double2* pre, double2* c, int64_t total, i
 void chirp_post(const double2* c, const double2* post, double* y, int64_t total, int64_t m, int64_t I, double scale,
                 hipStream_t s);
 template <typename T> void to_f64(const void* src, double* dst, int64_t n, double add0, hipStream_t s);
+void square_f64(const double* src, double* dst, int64_t n, hipStream_t s);   // dst = src^2 (in place allowed)
 // nclamp[0] counts the clamped entries; nclamp[1] / nclamp[2] receive max D / max 1/D (finite
 // values, as the bits of positive doubles) for pack_scale
 void clamp_spectrum(const double* Draw, double* out3, int64_t M, double clamp_min, unsigned long long* nclamp,

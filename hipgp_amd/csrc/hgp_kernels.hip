@@ -90,6 +90,21 @@ void to_f64(const void* src, double* dst, int64_t n, double add0, hipStream_t s)
 template void to_f64<float>(const void*, double*, int64_t, double, hipStream_t);
 template void to_f64<double>(const void*, double*, int64_t, double, hipStream_t);
 
+// dst = src^2 elementwise (fp64; in place allowed): the m-grid values of the squared generator
+// s^2 that HGP_OP_RSQ's spectrum is built from (hgp_api.hip ensure_rsq_t)
+__global__ void k_square_f64(const double* src, double* dst, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const double v = src[i];
+    dst[i] = v * v;
+  }
+}
+
+void square_f64(const double* src, double* dst, int64_t n, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_square_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n);
+}
+
 // D = max(Draw, clamp); write [D | 1/D | sqrt(D)] (3 x M) and count clamped entries; the
 // maxima of D and 1/D (pack_scale) by a grid-stride sweep of <= 1024 blocks, one atomic each per
 // block (one per 256 elements serialised on two words: 97 us at 1M elements)

@@ -168,7 +168,7 @@ class ToeplitzPlan:
 
     # -- operators ---------------------------------------------------------------------------
     def apply(self, op, x, out=None):
-        nin = self.Mprime if op == _lib.OP_R else self.M
+        nin = self.Mprime if op in (_lib.OP_R, _lib.OP_RSQ) else self.M
         nout = self.Mprime if op == _lib.OP_RT else self.M
         x = self._vec(x, "x", nin)
         if out is None:
@@ -225,7 +225,10 @@ class ToeplitzPlan:
 
     def column_grad(self, op, x, g):
         """d/dcolumn of sum(g * op(x)) through the operator's spectrum (hgp_plan_column_grad),
-        (M,) in the plan dtype; x, g shaped like op's input / output (`toeplitz_tensor.py:20-125`)."""
+        (M,) in the plan dtype; x, g shaped like op's input / output (`toeplitz_tensor.py:20-125`).
+        OP_RSQ has no gradient."""
+        if op == _lib.OP_RSQ:
+            raise _lib.HipgpError("OP_RSQ has no column gradient (hgp_plan_column_grad refuses it)")
         nin = self.Mprime if op == _lib.OP_R else self.M
         nout = self.Mprime if op == _lib.OP_RT else self.M
         x = self._vec(x, "x", nin)

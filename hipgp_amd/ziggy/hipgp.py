@@ -153,6 +153,19 @@ class ToeplitzInducingGP(SviGP):
     def get_kl_to_prior(self, qm, qS):
         raise NotImplementedError
 
+    # ---- the posterior on the whole inducing grid ---------------------------------------------
+    _NO_GRID_POSTERIOR = ("the inducing-grid posterior needs the whitened mean-field family "
+                          "(MeanFieldToeplitzGP, whitened_type='ziggy'): its variance diag(R S R^T) is the "
+                          "circulant operator R o R applied to diag S only for a diagonal S -- a "
+                          "block-diagonal S has no circulant R S R^T diagonal, and cholesky whitening has "
+                          "no circulant R at all")
+
+    def grid_posterior(self, prior=False, Kmm=None):
+        raise NotImplementedError(self._NO_GRID_POSTERIOR)
+
+    def sample_grid(self, n, prior=False, generator=None, eps=None, Kmm=None):
+        raise NotImplementedError(self._NO_GRID_POSTERIOR)
+
     # ---- ELBO --------------------------------------------------------------------------------
     def compute_batch_an(self, xbatch, ybatch, noise_std_batch=None, qm=None, qS=None, Knm=None,
                          Knn_diag=None, kn=None, maxiter_cg=10, integrated_obs=False,
@@ -408,6 +421,71 @@ class MeanFieldToeplitzGP(ToeplitzInducingGP):
                 d0 = Kmm.inv_matmul(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
             qm, qS = self.standard_variational_params()
             return Kmm.rt_stats(d0, qm, qS)
+
+    # ---- the posterior on the whole inducing grid (no reference counterpart: the reference leaves
+    # sample() a TODO, `hipgp.py:111-115`, and predicts point by point) ---------------------------
+    def _grid_kmm(self, Kmm):
+        """`predict_stats`' rule for a caller's Kmm: it must have the operator, else a fresh one."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_GRID_POSTERIOR)
+        if Kmm is None or not hasattr(Kmm, "_matmul_by_Rsq"):
+            Kmm = self.toeplitz()
+        return Kmm
+
+    def _grid_rows(self, Kmm, t, nrows):
+        """t as the (nrows, M') operator input in the model dtype on the grid's device."""
+        if hasattr(Kmm, "set_batch_shape"):
+            Kmm.set_batch_shape((nrows,))
+        return t.detach().reshape(nrows, self.Mprime).to(device=self.xgrids[0].device, dtype=self.dtype).contiguous()
+
+    def grid_posterior(self, prior=False, Kmm=None):
+        """(mean, sd) of the variational posterior of the inducing values u on the whole inducing
+        grid, device tensors shaped (m_1, ..., m_d), from two operator applications and no solve.
+
+        The whitened family is u = R v, v ~ N(qm, diag qS), so E[u] = R qm (HGP_OP_R) and
+        Var[u]_j = sum_k R_jk^2 qS_k = ((R o R) qS)_j (HGP_OP_RSQ: R is the crop of a circulant with
+        generator s = IFFT_n(sqrt D), so R o R is the crop of the circulant with generator s^2).
+        prior=True: (0, sqrt((R o R) 1)), the prior sd sqrt(K_jj) = sqrt(column[0]) where no
+        eigenvalue is clamped.
+
+        This is the posterior of the inducing values u, whose prior covariance is K INCLUDING the
+        nugget -- not that of f(x_j), which `predict` computes.  On the grid Knm = K - jitter I, so
+        the two means are related exactly by predict_mean(xinduce) = u - jitter K^-1 u, u = R qm."""
+        with torch.no_grad():
+            Kmm = self._grid_kmm(Kmm)
+            dims = tuple(len(g) for g in self.xgrids)
+            qm, qS = self.standard_variational_params()
+            if prior:
+                mean = torch.zeros(dims, dtype=self.dtype, device=self.xgrids[0].device)
+                w = torch.ones_like(qS)
+            else:
+                mean = Kmm._matmul_by_R(self._grid_rows(Kmm, qm, 1)).reshape(dims)
+                w = qS
+            var = Kmm._matmul_by_Rsq(self._grid_rows(Kmm, w, 1))
+            # a sum of non-negative terms; the transforms' rounding can leave -eps where it is ~0
+            return mean, torch.sqrt(var.clamp_min(0)).reshape(dims)
+
+    def sample_grid(self, n, prior=False, generator=None, eps=None, Kmm=None):
+        """n joint draws of the inducing values on the inducing grid, (n, m_1, ..., m_d) on the
+        device: u = R (qm + sqrt(qS) * eps), or R eps with prior=True (one HGP_OP_R of n rows).
+        eps (n, M') standard normal draws makes the result reproducible; otherwise they come from
+        torch.randn with `generator`, shifted and scaled in place (one (n, M') buffer).  The same
+        quantity as `grid_posterior` (u, nugget included), whose mean and sd the draws have."""
+        with torch.no_grad():
+            Kmm = self._grid_kmm(Kmm)
+            dims = tuple(len(g) for g in self.xgrids)
+            dev = self.xgrids[0].device
+            if eps is None:
+                v = torch.randn((int(n), self.Mprime), generator=generator, dtype=self.dtype, device=dev)
+            else:
+                if tuple(eps.shape) != (int(n), self.Mprime):
+                    raise ValueError(f"eps must be (n, M') = ({int(n)}, {self.Mprime}), got {tuple(eps.shape)}")
+                v = eps.detach().to(device=dev, dtype=self.dtype, copy=True)     # the caller's eps stays
+            if not prior:
+                qm, qS = self.standard_variational_params()
+                row = lambda t: t.detach().reshape(1, -1).to(device=dev, dtype=self.dtype)
+                v.mul_(torch.sqrt(row(qS))).add_(row(qm))
+            return Kmm._matmul_by_R(self._grid_rows(Kmm, v, int(n))).reshape(int(n), *dims)
 
     def fit_stats(self, Knm, ybatch, Knn_diag, noise_std_batch=None, maxiter_cg=10, Kmm=None):
         """`batch_stats` of kn = R^T K^-1 Knm^T (`hipgp.py:234-250`) without the (bsz, M') kn:

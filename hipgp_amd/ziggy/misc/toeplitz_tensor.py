@@ -8,6 +8,7 @@ Operator map (reference line -> here):
   rt_stats (no reference line)          -> hgp_rt_stats (R^T with predict's three dots fused in)
   rt_fit_stats (no reference line)      -> hgp_rt_fit_stats (those dots and the lam column sums)
   _matmul_by_R     (:99-112)            -> HGP_OP_R
+  _matmul_by_Rsq (no reference line)    -> HGP_OP_RSQ (R squared elementwise, the grid posterior's variance)
   _matmul_by_Cinv  (:114-125)           -> HGP_OP_CINV
   _solve / conj_grad2 (:54-68)          -> hgp_pcg_solve (device-side early-exit flag)
 The spectrum attributes C, D, D_sqrt, Di, Di_sqrt are materialised lazily (they are
@@ -127,6 +128,16 @@ class ToeplitzTensor:
     def _matmul_by_R(self, vec):
         self._check_batch()
         return self._op(_lib.OP_R, vec.reshape(vec.shape[0], -1))
+
+    def _matmul_by_Rsq(self, vec):
+        """(R o R) vec, the elementwise square of R as an operator (HGP_OP_RSQ): vec (bsz, M') ->
+        (bsz, M), so `_matmul_by_Rsq(qS)` is the marginal variance of u = R v, v ~ N(qm, diag qS).
+        No reference line; the first call after the spectrum set-up builds a second spectrum table
+        of R's size.  No autograd."""
+        self._check_batch()
+        if torch.is_grad_enabled() and (vec.requires_grad or self.column.requires_grad):
+            raise RuntimeError("_matmul_by_Rsq has no backward: call it under torch.no_grad() or on detached inputs")
+        return self._plan.apply(_lib.OP_RSQ, vec.reshape(vec.shape[0], -1))
 
     def _matmul_by_Cinv(self, vec):
         self._check_batch()

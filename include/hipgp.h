@@ -29,7 +29,7 @@ extern "C" {
 typedef struct hgp_plan hgp_plan;
 
 enum { HGP_F32 = 0, HGP_F64 = 1 };
-enum { HGP_OP_K = 0, HGP_OP_CINV = 1, HGP_OP_RT = 2, HGP_OP_R = 3 };
+enum { HGP_OP_K = 0, HGP_OP_CINV = 1, HGP_OP_RT = 2, HGP_OP_R = 3, HGP_OP_RSQ = 4 };
 enum { HGP_SPEC_D = 0, HGP_SPEC_DSQRT = 1, HGP_SPEC_DI = 2 };
 enum { HGP_LAYOUT_ROWS = 0, HGP_LAYOUT_COLS = 1 };
 enum { HGP_KERN_SQEXP = 0, HGP_KERN_MATERN12 = 1, HGP_KERN_MATERN32 = 2, HGP_KERN_MATERN52 = 3,
@@ -70,8 +70,20 @@ int hgp_plan_set_column(hgp_plan* plan, const void* column, double jitter, doubl
  *   HGP_OP_CINV : C^-1 block v   x:(nrhs,M)  -> y:(nrhs,M)    toeplitz_tensor.py:114-125
  *   HGP_OP_RT   : R^T v          x:(nrhs,M)  -> y:(nrhs,M')   toeplitz_tensor.py:85-97
  *   HGP_OP_R    : R w            x:(nrhs,M') -> y:(nrhs,M)    toeplitz_tensor.py:99-112
- * (same four ops as ToeplitzMatmul.forward "gram"/"circ_inv"/"RTv"/"Rv",
- *  toeplitz_expanded.py:139-189).  x and y must not alias. */
+ *   HGP_OP_RSQ  : (R o R) w      x:(nrhs,M') -> y:(nrhs,M)    no reference counterpart
+ * (the first four are ToeplitzMatmul.forward "gram"/"circ_inv"/"RTv"/"Rv",
+ *  toeplitz_expanded.py:139-189).  x and y must not alias.
+ * HGP_OP_RSQ is the elementwise square of R as an operator: with s = IFFT_n(sqrt D) the even,
+ * n-periodic generator of R (R[j,k] = s[(j - k) mod n], j on the m-grid, k on the n-grid),
+ *   y[q, j] = sum_k s[(j - k) mod n]^2 x[q, k],
+ * so (R o R) qS is the marginal variance of u = R v, v ~ N(qm, diag qS) (the inducing-grid
+ * posterior of the whitened mean-field family; the reference has no such route and leaves
+ * sample() a TODO, ziggy/hipgp.py:111-115).  It runs HGP_OP_R's pass sequence on a second
+ * spectrum table of R's layout and size, built from the set column on the first HGP_OP_RSQ call
+ * after a hgp_plan_set_column (that call allocates and must not run inside a stream capture,
+ * else HGP_E_STATE); plans that never ask hold no such table.  Plans whose R / R^T take the
+ * full-grid route return HGP_E_UNSUPPORTED.  hgp_toeplitz_apply only: the pass-split, slab and
+ * column-gradient entry points refuse HGP_OP_RSQ. */
 int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs);
 
 /* out3[n*3 + c] = (kn_n.qm, |kn_n|^2, kn_n^2.qS) for kn_n = R^T d_n, without writing kn
@@ -309,7 +321,8 @@ int hgp_plan_info(const hgp_plan* plan, int64_t* M, int64_t* Mprime, int64_t* L_
                   int64_t* L_R);
 
 /* Device memory a plan holds: scratch (operator workspaces, CG vectors, set-up scratch; all
- * re-allocated on demand) and tables (twiddles, Bluestein DCT tables, spectra).
+ * re-allocated on demand) and tables (twiddles, Bluestein DCT tables, spectra; HGP_OP_RSQ's
+ * spectrum from its first use until the next hgp_plan_set_column).
  * hgp_plan_trim frees the scratch (after synchronising the plan's streams) and keeps the tables,
  * so an idle plan kept for re-use holds only what its next set-up needs. */
 int hgp_plan_mem(const hgp_plan* plan, int64_t* scratch_bytes, int64_t* table_bytes);
