@@ -33,6 +33,7 @@ EXPORTS = (
     "hgp_slab_info", "hgp_slab_pass", "hgp_plan_mem", "hgp_plan_trim",
     "hgp_slab_pass_ex", "hgp_slab_cg_xr", "hgp_slab_cg_check", "hgp_slab_cg_p",
     "hgp_meanfield_rowdots", "hgp_meanfield_cols", "hgp_rt_stats", "hgp_rt_fit_stats",
+    "hgp_rt_block_stats",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -61,6 +62,7 @@ def lib():
         "hgp_toeplitz_apply": (i32, [vp, i32, vp, vp, i64]),
         "hgp_rt_stats": (i32, [vp, vp, i64, vp, vp, vp]),
         "hgp_rt_fit_stats": (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
+        "hgp_rt_block_stats": (i32, [vp, vp, i64, pi64, i64, vp, vp, vp, vp, vp]),
         "hgp_pcg_solve": (i32, [vp, vp, vp, i64, i32, dbl, i32, i32, pi32]),
         "hgp_pcg_begin": (i32, [vp, vp, vp, i64, i32, i32]),
         "hgp_pcg_step": (i32, [vp, dbl, pi32]),

@@ -1707,6 +1707,30 @@ int rt_fit_stats_t(hgp_plan* P, const void* dv, int64_t nrhs, const void* qm, co
   return 0;
 }
 
+// The block family's sums of kn = R^T d (hgp_rt_block_stats): a gram entry pairs kn values of
+// different grid rows, which no thread group of R^T's last pass holds together, so this is no pass
+// epilogue.  R^T runs into plan scratch (st_kn) one piece of RHS at a time, as the unfused
+// rt_stats_t does, and block_stats_rt consumes each piece once, the gram continuing from piece to
+// piece on the plan's stream.  Each piece re-reads and re-writes the gram (bs M' values, as much as
+// bs rows of kn), hence the default piece of at least bs RHS: max(HGP_RT_STATS_PIECE / M', bs).
+template <typename T>
+int rt_block_stats_t(hgp_plan* P, const void* dv, int64_t nrhs, const BlockGeom& g, int64_t piece_rhs, const void* qm,
+                     const void* S, const void* iv, void* out3, void* gram) {
+  int64_t piece = piece_rhs > 0 ? piece_rhs : std::max<int64_t>(HGP_RT_STATS_PIECE / P->Mp, g.bs);
+  piece = std::max<int64_t>(1, std::min<int64_t>(nrhs, piece));
+  HGP_TRY(P->st_kn.ensure((size_t)(piece * P->Mp) * sizeof(T)));
+  HGP_TRY(P->st_part.ensure((size_t)(3 * piece * block_stats_groups(g)) * sizeof(T)));
+  for (int64_t q0 = 0; q0 < nrhs; q0 += piece) {
+    const int64_t qn = std::min(piece, nrhs - q0);
+    HGP_TRY(run_op<T>(P, HGP_OP_RT, reinterpret_cast<const T*>(dv) + q0 * P->M, P->st_kn.ptr, qn, nullptr, nullptr,
+                      nullptr));
+    hipError_t e = block_stats_rt(P->dtype, g, P->st_kn.ptr, qn, iv ? reinterpret_cast<const T*>(iv) + q0 : nullptr, S,
+                                  qm, gram, q0 > 0, P->st_part.ptr, reinterpret_cast<T*>(out3) + q0 * 3, P->stream);
+    if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rt_block_stats: ") + hipGetErrorString(e));
+  }
+  return 0;
+}
+
 #define DISPATCH(P, FN, ...) ((P)->dtype == HGP_F64 ? FN<double>(__VA_ARGS__) : FN<float>(__VA_ARGS__))
 
 int check_plan(const hgp_plan* P) {
@@ -1961,6 +1985,31 @@ int hgp_rt_fit_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm
     return 0;
   }
   return DISPATCH(plan, rt_fit_stats_t, plan, d, nrhs, qm, qS, ivar, out3, lam);
+}
+
+int hgp_rt_block_stats(hgp_plan* plan, const void* d, int64_t nrhs, const int64_t* blocks, int64_t piece_rhs,
+                       const void* qm, const void* S, const void* ivar, void* out3, void* gram) {
+  HGP_TRY(check_plan(plan));
+  if (nrhs < 0 || nrhs > (int64_t)1 << 30) return fail(HGP_E_ARG, "hgp_rt_block_stats: nrhs out of range");
+  if (piece_rhs < 0) return fail(HGP_E_ARG, "hgp_rt_block_stats: piece_rhs < 0");
+  if (blocks == nullptr) return fail(HGP_E_ARG, "hgp_rt_block_stats: null blocks");
+  if (nrhs > 0 && (d == nullptr || qm == nullptr || out3 == nullptr))
+    return fail(HGP_E_ARG, "hgp_rt_block_stats: null d / qm / out3");
+  if (nrhs > 0 && gram != nullptr && ivar == nullptr) return fail(HGP_E_ARG, "hgp_rt_block_stats: null ivar");
+  if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  if (plan->d != plan->ndim_user)
+    return fail(HGP_E_UNSUPPORTED, "hgp_rt_block_stats: grids with a size-1 axis have no block tiling");
+  BlockGeom g;
+  const char* why = nullptr;
+  if (block_geom(plan->d, plan->n, blocks, &g, &why) != 0)
+    return fail(HGP_E_UNSUPPORTED, std::string("hgp_rt_block_stats: ") + why);
+  HGP_TRY(use_device(plan));
+  if (nrhs == 0) {                                    // the empty sum
+    if (gram != nullptr)
+      HIP_TRY(hipMemsetAsync(gram, 0, (size_t)(g.nblk * g.bs * g.bs) * plan->esz, plan->stream));
+    return 0;
+  }
+  return DISPATCH(plan, rt_block_stats_t, plan, d, nrhs, g, piece_rhs, qm, S, ivar, out3, gram);
 }
 
 int hgp_toeplitz_apply_pass(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs, int pass) {

@@ -109,6 +109,13 @@ struct BlockGeom {
 int block_geom(int ndim, const int64_t* dims, const int64_t* blocks, BlockGeom* g, const char** why);
 hipError_t block_stats(int dtype, const BlockGeom& g, const void* kn, int64_t nrhs, const void* iv, const void* S,
                        void* gram, void* knSkn, void* trSG, hipStream_t s);
+// workgroups of the block-statistics kernels (the row partials are [row][workgroup])
+int64_t block_stats_groups(const BlockGeom& g);
+// one piece of kn (nrhs x Mp) into the streamed block statistics (hgp_rt_block_stats): gram (may be
+// NULL, then iv too) continues from its stored values when cont != 0; out3[n] = (kn_n . qm, |kn_n|^2,
+// kn_n^T S kn_n), the third 0 when S is NULL; part: 3 nrhs block_stats_groups(g) values of scratch
+hipError_t block_stats_rt(int dtype, const BlockGeom& g, const void* kn, int64_t nrhs, const void* iv, const void* S,
+                          const void* qm, void* gram, int cont, void* part, void* out3, hipStream_t s);
 hipError_t kuf_semi_grid(int dtype, int kind, int method, int ndim, const int64_t* m, const void* const* grids,
                          const void* x, int64_t nobs, double sig2, double ell, const void* nodes,
                          const void* weights, int npts, void* out, hipStream_t s);

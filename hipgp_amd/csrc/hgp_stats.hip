@@ -530,6 +530,221 @@ hipError_t block_stats_t(const BlockGeom& g, const void* kn, int64_t nrhs, const
   return hipSuccess;
 }
 
+// ---- the block family's statistics of kn = R^T d streamed a piece of RHS at a time (hgp_rt_block_stats)
+// k_block_stats's thread map, LDS tile and summation order, with three changes:
+//   * cont != 0: the gram accumulators start from the stored gram entry (each entry has one owner
+//     thread per launch and the pieces' launches are ordered on one stream, so the plain
+//     read-modify-write needs no atomics; a stored accumulator reloads exactly, so the sum over
+//     the RHS is the one-launch sum, piece boundaries or not);
+//   * qm of the workgroup's columns is staged in LDS like colofs, and the pass that forms
+//     kn_n^T S kn_n (lane = RHS, wave = row) also sums kn_n . qm and |kn_n|^2 over the rows it
+//     visits -- every column of the workgroup is one row of exactly one wave -- so the piece is
+//     read once for the gram and all three row dots;
+//   * the partials are part[(n * 3 + c)][workgroup], c = (kn.qm, |kn|^2, kn^T S kn), reduced by
+//     reduce_rows straight into out3's [n][3] layout.  S == nullptr: the third dot is 0.
+// No trace output: the streamed step takes kn^T S kn per row.
+template <typename T>
+__host__ __device__ inline size_t bkr_lds(int nbw, int bs, int TA, bool SL) {
+  const int ncol = nbw * bs;
+  return (size_t)(BK_NB * bk_pitch(ncol, TA) + BK_NB + 12 * BK_NB + ncol + (SL ? nbw * bs * bs : 0)) * sizeof(T) +
+         (size_t)ncol * sizeof(int);
+}
+
+template <typename T, int TA, bool SL>
+__global__ __launch_bounds__(BK_THREADS) void k_block_stats_rt(BlockGeom g, const T* __restrict__ kn, int nrhs,
+                                                              const T* __restrict__ iv, const T* __restrict__ S,
+                                                              const T* __restrict__ qm, T* __restrict__ gram,
+                                                              T* __restrict__ part, int cont) {
+  extern __shared__ unsigned char smem_raw[];
+  T* smem = reinterpret_cast<T*>(smem_raw);
+  const int bs = g.bs, nbw = g.nbw, bs2 = bs * bs;
+  const int ncol = nbw * bs, pitch = bk_pitch(ncol, TA);
+  T* Kt = smem;                                   // [BK_NB][pitch]
+  T* ivs = Kt + BK_NB * pitch;                    // [BK_NB]
+  T* Q = ivs + BK_NB;                             // [3][4][BK_NB]
+  T* qms = Q + 12 * BK_NB;                        // [ncol]
+  T* Ss = qms + ncol;                             // [nbw][bs][bs] (SL)
+  int* colofs = reinterpret_cast<int*>(Ss + (SL ? nbw * bs2 : 0));   // [ncol], -1 = no block
+  const int64_t beta0 = (int64_t)blockIdx.x * nbw;
+  const int nvalid = (int)min<int64_t>(nbw, g.nblk - beta0);
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  for (int col = t; col < ncol; col += BK_THREADS) {
+    const int bl = col / bs, i = col - bl * bs;
+    int64_t rem = beta0 + bl, irem = i, flat = 0, stride = 1;
+    for (int a = g.d - 1; a >= 0; --a) {
+      const int64_t c = rem % g.nb[a], ii = irem % g.b[a];
+      rem /= g.nb[a];
+      irem /= g.b[a];
+      flat += (c * g.b[a] + ii) * stride;
+      stride *= g.n[a];
+    }
+    colofs[col] = bl < nvalid ? (int)flat : -1;
+    qms[col] = bl < nvalid ? qm[flat] : (T)0;
+  }
+  if (SL) {
+    const T* Sg = S + beta0 * bs2;
+    for (int q = t; q < nbw * bs2; q += BK_THREADS) Ss[q] = (q < nvalid * bs2) ? Sg[q] : (T)0;
+  }
+  constexpr int NA = TA > 0 ? TA : 1;
+  const int gi = t >> 4, gj = t & 15;
+  const int nent = nvalid * bs2;
+  const bool gram_thread = gram != nullptr && (TA > 0 || t < nent);
+  T* gb = gram_thread ? gram + beta0 * bs2 : nullptr;
+  T acc[NA][NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int b = 0; b < NA; ++b) {
+      const int i = gi + 16 * a, j = gj + 16 * b;
+      acc[a][b] = (TA > 0 && cont && gram_thread && i < bs && j < bs) ? gb[i * bs + j] : (T)0;
+    }
+  // TA = 0: entries e = t + 256 r (r < BK_ER) of the workgroup's contiguous gram slab
+  T acc0[BK_ER];
+  int oi[BK_ER], oj[BK_ER];
+#pragma unroll
+  for (int r = 0; r < BK_ER; ++r) {
+    acc0[r] = (TA == 0 && cont && gram_thread && t + BK_THREADS * r < nent) ? gb[t + BK_THREADS * r] : (T)0;
+    const int e = min(t + BK_THREADS * r, nbw * bs2 - 1);
+    const int bl = e / bs2, ij = e - bl * bs2, i = ij / bs;
+    oi[r] = bl * bs + i;
+    oj[r] = bl * bs + (ij - i * bs);
+  }
+  const int nwg = gridDim.x;
+  __syncthreads();
+  for (int n0 = 0; n0 < nrhs; n0 += BK_NB) {
+    const int nn = min(BK_NB, nrhs - n0);
+    // BK_UNR independent row loads in flight.  Columns >= ncol (tile padding) stay unset: they only
+    // feed gram entries i or j >= bs, which are never stored.
+    for (int col = lane; col < ncol; col += 64) {
+      const int o = colofs[col];
+      for (int rn0 = w; rn0 < nn; rn0 += 4 * BK_UNR) {
+        T v[BK_UNR];
+#pragma unroll
+        for (int u = 0; u < BK_UNR; ++u) {
+          const int rn = rn0 + 4 * u;
+          v[u] = 0;
+          if (o >= 0 && rn < nn) v[u] = kn[(int64_t)(n0 + rn) * g.Mp + o];
+        }
+#pragma unroll
+        for (int u = 0; u < BK_UNR; ++u)
+          if (rn0 + 4 * u < nn) Kt[(rn0 + 4 * u) * pitch + col] = v[u];
+      }
+    }
+    if (t < BK_NB) ivs[t] = (t < nn && iv != nullptr) ? iv[n0 + t] : (T)0;   // iv may be NULL without gram
+    __syncthreads();
+    if (TA == 0 && gram_thread) {
+      for (int k = 0; k < nn; ++k) {
+        const T ivk = ivs[k];
+        const T* kr = Kt + k * pitch;
+#pragma unroll
+        for (int r = 0; r < BK_ER; ++r)
+          if (t + BK_THREADS * r < nent) acc0[r] += ivk * kr[oi[r]] * kr[oj[r]];
+      }
+    } else if (gram_thread) {
+      const T* ki = Kt + gi;
+      const T* kj = Kt + gj;
+      for (int k = 0; k < nn; ++k) {
+        const T ivk = ivs[k];
+        T vi[NA], vj[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+          vi[a] = ivk * ki[k * pitch + 16 * a];
+          vj[a] = kj[k * pitch + 16 * a];
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+          for (int b = 0; b < NA; ++b) acc[a][b] += vi[a] * vj[b];
+      }
+    }
+    {
+      T d0 = 0, d1 = 0, qv = 0;
+      if (lane < nn) {
+        const T* kr = Kt + lane * pitch;
+        for (int row = w; row < nvalid * bs; row += 4) {
+          const T kv = kr[row];
+          d0 += kv * qms[row];
+          d1 += kv * kv;
+          if (S != nullptr) {
+            const int bl = row / bs, i = row - bl * bs;
+            const T* srow = SL ? Ss + (bl * bs + i) * bs : S + ((beta0 + bl) * bs + i) * bs;
+            const T* kb = kr + bl * bs;
+            T u = 0;
+            for (int j = 0; j < bs; ++j) u += srow[j] * kb[j];
+            qv += kv * u;
+          }
+        }
+      }
+      Q[w * BK_NB + lane] = d0;
+      Q[(4 + w) * BK_NB + lane] = d1;
+      Q[(8 + w) * BK_NB + lane] = qv;
+    }
+    __syncthreads();
+    if (t < 3 * BK_NB && lane < nn) {          // wave c (< 3) finishes dot c, lane = RHS
+      const T* q = Q + w * 4 * BK_NB + lane;
+      part[((int64_t)(n0 + lane) * 3 + w) * nwg + blockIdx.x] = (q[0] + q[BK_NB]) + (q[2 * BK_NB] + q[3 * BK_NB]);
+    }
+    __syncthreads();
+  }
+  if (TA == 0 && gram_thread) {
+#pragma unroll
+    for (int r = 0; r < BK_ER; ++r) {
+      const int e = t + BK_THREADS * r;
+      if (e < nent) gb[e] = acc0[r];
+    }
+  } else if (gram_thread) {        // TA > 0: one block per workgroup
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+      for (int b = 0; b < NA; ++b) {
+        const int i = gi + 16 * a, j = gj + 16 * b;
+        if (i < bs && j < bs) gb[i * bs + j] = acc[a][b];
+      }
+  }
+}
+
+template <typename T, int TA>
+void launch_block_stats_rt(const BlockGeom& g, int64_t grid, const void* kn, int nrhs, const void* iv, const void* S,
+                           const void* qm, void* gram, void* part, int cont, hipStream_t s) {
+  const bool sl = S != nullptr && bkr_lds<T>(g.nbw, g.bs, TA, true) <= BK_LDS_MAX;
+  const size_t lds = bkr_lds<T>(g.nbw, g.bs, TA, sl);
+  auto launch = [&](auto kern) {
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BK_THREADS), lds, s, g, (const T*)kn, nrhs, (const T*)iv,
+                       (const T*)S, (const T*)qm, (T*)gram, (T*)part, cont);
+  };
+  if (sl) launch(k_block_stats_rt<T, TA, true>);
+  else launch(k_block_stats_rt<T, TA, false>);
+}
+
+template <typename T>
+hipError_t block_stats_rt_t(const BlockGeom& g, const void* kn, int64_t nrhs, const void* iv, const void* S,
+                            const void* qm, void* gram, int cont, void* part, void* out3, hipStream_t s) {
+  if (nrhs <= 0) return hipSuccess;
+  const int64_t grid = block_stats_groups(g);
+  const int TA = g.bs <= 16 ? 0 : (g.bs + 15) / 16;
+  switch (TA) {
+    case 0: launch_block_stats_rt<T, 0>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    case 2: launch_block_stats_rt<T, 2>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    case 3: launch_block_stats_rt<T, 3>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    case 4: launch_block_stats_rt<T, 4>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    case 5: launch_block_stats_rt<T, 5>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    case 6: launch_block_stats_rt<T, 6>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    case 7: launch_block_stats_rt<T, 7>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+    default: launch_block_stats_rt<T, 8>(g, grid, kn, (int)nrhs, iv, S, qm, gram, part, cont, s); break;
+  }
+  reduce_rows<T>(part, (int)grid, (int)(3 * nrhs), out3, s);
+  return hipGetLastError();
+}
+
+int64_t block_stats_groups(const BlockGeom& g) { return (g.nblk + g.nbw - 1) / g.nbw; }
+
+hipError_t block_stats_rt(int dtype, const BlockGeom& g, const void* kn, int64_t nrhs, const void* iv, const void* S,
+                          const void* qm, void* gram, int cont, void* part, void* out3, hipStream_t s) {
+  if (dtype == HGP_F64) return block_stats_rt_t<double>(g, kn, nrhs, iv, S, qm, gram, cont, part, out3, s);
+  return block_stats_rt_t<float>(g, kn, nrhs, iv, S, qm, gram, cont, part, out3, s);
+}
+
 int block_geom(int ndim, const int64_t* dims, const int64_t* blocks, BlockGeom* g, const char** why) {
   if (ndim < 2 || ndim > 3) { *why = "block family supports 2-D and 3-D grids only (util.py:88)"; return -1; }
   g->d = ndim;

@@ -223,6 +223,47 @@ class ToeplitzPlan:
             self._report_ws()
         return out, lam
 
+    def rt_block_stats(self, d, blocks, qm, S=None, ivar=None, gram=True, piece_rhs=0):
+        """(out3 (B, 3), gram (nblk, bs, bs) or None) of kn = R^T d for the block-diagonal family,
+        without the (B, M') kn (hgp_rt_block_stats): out3 rows (kn.qm, |kn|^2, kn^T S kn), gram[blk] =
+        sum_n ivar[n] kn_blk kn_blk^T.  d (B, M); blocks: the block sides on the expanded grid; qm
+        (M',) or (M', 1); S (nblk, bs, bs) or None (third dot 0); ivar (B,), needed with gram=True;
+        piece_rhs: right-hand sides per streamed piece, 0 for the library's default.
+        Deterministic."""
+        d = self._vec(d, "d", self.M)
+        B = d.shape[0]
+        blocks = [int(b) for b in blocks]
+        if len(blocks) != len(self.dims):
+            raise ValueError(f"blocks has {len(blocks)} sides, the grid has {len(self.dims)} axes")
+        if any(b <= 0 for b in blocks):
+            raise ValueError(f"block sides must be positive, got {blocks}")
+        bs = int(np.prod(blocks))
+        nblk = int(np.prod([n // b for n, b in zip(self.ndims, blocks)]))
+        if gram and ivar is None:
+            raise ValueError("gram=True needs ivar")
+        want = {"qm": (qm, self.Mprime), "S": (S, nblk * bs * bs), "ivar": (ivar if gram else None, B)}
+        vecs = {}
+        for name, (t, n) in want.items():
+            if t is None:
+                vecs[name] = None
+                continue
+            _lib.require_device_tensor(t, name)
+            if t.dtype != self.dtype or t.device != self.device:
+                raise TypeError(f"{name} is {t.dtype} on {t.device}, plan is {self.dtype} on {self.device}")
+            if t.numel() != n:
+                raise ValueError(f"{name} has {t.numel()} values, expected {n}")
+            vecs[name] = t.detach().reshape(-1).contiguous()
+        out = torch.empty((B, 3), dtype=self.dtype, device=self.device)
+        G = torch.empty((nblk, bs, bs), dtype=self.dtype, device=self.device) if gram else None
+        self._bind_stream()
+        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        blk = (ctypes.c_int64 * len(blocks))(*blocks)
+        check(lib().hgp_rt_block_stats(self._h, p(d), B, blk, int(piece_rhs), p(vecs["qm"]), p(vecs["S"]),
+                                       p(vecs["ivar"]), p(out), p(G)))
+        if not _ws_warned:
+            self._report_ws()
+        return out, G
+
     def column_grad(self, op, x, g):
         """d/dcolumn of sum(g * op(x)) through the operator's spectrum (hgp_plan_column_grad),
         (M,) in the plan dtype; x, g shaped like op's input / output (`toeplitz_tensor.py:20-125`).

@@ -150,6 +150,18 @@ class ToeplitzInducingGP(SviGP):
         (Knm untouched) where the family, the whitening or a caller's Kmm has no fused route."""
         return None
 
+    def streamed_predict_stats(self, Knm, maxiter_cg=50, Kmm=None):
+        """`predict_stats` for `predict(streamed=True)`: the same (bsz, 3) rows from kn streamed a
+        piece of right-hand sides at a time (hgp_rt_block_stats), or None (Knm untouched) where the
+        family, the whitening or a caller's Kmm has no streamed route."""
+        return None
+
+    def streamed_fit_stats(self, Knm, ybatch, Knn_diag, noise_std_batch=None, maxiter_cg=10, Kmm=None):
+        """`fit_stats` for `elbo_and_grad(streamed=True)`: the dict of `batch_stats` from kn streamed
+        a piece of right-hand sides at a time (hgp_rt_block_stats), or None (Knm untouched) where the
+        family, the whitening or a caller's Kmm has no streamed route."""
+        return None
+
     def get_kl_to_prior(self, qm, qS):
         raise NotImplementedError
 
@@ -207,21 +219,32 @@ class ToeplitzInducingGP(SviGP):
 
     def elbo_and_grad(self, xbatch, ybatch, noise_std_batch=None, maxiter_cg=10, integrated_obs=False,
                       semi_integrated_estimator="analytic", semi_integrated_samps=10,
-                      print_debug_info=False, Kmm=None, mc_offset=None, fused=None):
+                      print_debug_info=False, Kmm=None, mc_offset=None, fused=None, streamed=None):
         """ELBO estimate; sets theta1.grad / theta2.grad to minus the natural gradient
         (`hipgp.py:194-276`).  mc_offset: see `SviGP._make_grams` (sharded fits).
 
         fused=True takes the batch sums straight from the R^T pass (`fit_stats`, hgp_rt_fit_stats)
         where the family has them and no hyper-parameter gradient is asked for (the autograd ELBO
         needs kn), so the (bsz, M') kn is never allocated; every other case takes the materialised
-        path.  None reads HGP_FIT_FUSED (default off)."""
+        path.  None reads HGP_FIT_FUSED (default off).
+
+        streamed=True is the block family's route to the same end (`streamed_fit_stats`,
+        hgp_rt_block_stats: kn held one piece of right-hand sides at a time), tried first and under
+        the same condition; a family without it proceeds as if the keyword were off.  None reads
+        HGP_BLOCK_STREAMED (default off)."""
         assert self.parameterization == 'expectation-family', \
             "need parameterization=expectation-family when performing natural gradient descent"
         if fused is None:
             fused = os.environ.get("HGP_FIT_FUSED", "0") not in ("", "0")
+        if streamed is None:
+            streamed = os.environ.get("HGP_BLOCK_STREAMED", "0") not in ("", "0")
         Knm, Knn_diag = self._make_grams(xbatch, integrated_obs=integrated_obs,
                                          semi_integrated_estimator=semi_integrated_estimator,
                                          semi_integrated_samps=semi_integrated_samps, mc_offset=mc_offset)
+        if streamed and not self.hyper_grad_needed(noise_std_batch):
+            stats = self.streamed_fit_stats(Knm, ybatch, Knn_diag, noise_std_batch, maxiter_cg=maxiter_cg, Kmm=Kmm)
+            if stats is not None:
+                return self.apply_stats(stats, xbatch.shape[0])
         if fused and not self.hyper_grad_needed(noise_std_batch):
             stats = self.fit_stats(Knm, ybatch, Knn_diag, noise_std_batch, maxiter_cg=maxiter_cg, Kmm=Kmm)
             if stats is not None:
@@ -327,20 +350,28 @@ class ToeplitzInducingGP(SviGP):
         return torch.mean(an) - self.get_kl_to_prior(qm, qS) / self.N
 
     def predict(self, x, integrated_obs=False, semi_integrated_estimator="analytic",
-                semi_integrated_samps=10, maxiter_cg=50, Kmm=None, fused=None):
+                semi_integrated_samps=10, maxiter_cg=50, Kmm=None, fused=None, streamed=None):
         """E[f(x)] and sd[f(x)] (`hipgp.py:416-446`), returned on the CPU.
 
         fused=True takes kn.qm, |kn|^2 and kn^2.qS straight from the R^T pass (hgp_rt_stats) where
         the family has them (`predict_stats`), so the (bsz, M') kn and its temporaries are never
         allocated; families without it take the materialised path.  None reads HGP_PREDICT_FUSED
-        (default off)."""
+        (default off).
+
+        streamed=True is the block family's route (`streamed_predict_stats`, hgp_rt_block_stats: kn
+        held one piece of right-hand sides at a time), tried first; a family without it proceeds as
+        if the keyword were off.  None reads HGP_BLOCK_STREAMED (default off)."""
         if fused is None:
             fused = os.environ.get("HGP_PREDICT_FUSED", "0") not in ("", "0")
+        if streamed is None:
+            streamed = os.environ.get("HGP_BLOCK_STREAMED", "0") not in ("", "0")
         x = x.to(self.xgrids[0].device)
         Knm, Knn_diag = self._make_grams(x, integrated_obs=integrated_obs,
                                          semi_integrated_estimator=semi_integrated_estimator,
                                          semi_integrated_samps=semi_integrated_samps)
-        out3 = self.predict_stats(Knm, maxiter_cg=maxiter_cg, Kmm=Kmm) if fused else None
+        out3 = self.streamed_predict_stats(Knm, maxiter_cg=maxiter_cg, Kmm=Kmm) if streamed else None
+        if out3 is None and fused:
+            out3 = self.predict_stats(Knm, maxiter_cg=maxiter_cg, Kmm=Kmm)
         if out3 is not None:
             qm, _ = self.standard_variational_params()
             mu = out3[:, 0].reshape(-1, *qm.shape[1:])
@@ -693,7 +724,9 @@ class BlockToeplitzGP(ToeplitzInducingGP):
     """Block-diagonal variational covariance over neighbouring points of the (expanded) grid
     (`hipgp.py:527-691`).  qm lives in grid order, qS / theta2 in block order
     (num_blocks, block_size, block_size).  On the device the per-block statistics are one fused
-    kernel (hgp_block_stats): sum_n ivar_n kn_blk kn_blk^T and kn^T S kn in a single read of kn."""
+    kernel (hgp_block_stats): sum_n ivar_n kn_blk kn_blk^T and kn^T S kn in a single read of kn.
+    With streamed=True (`elbo_and_grad`, `predict`) the same sums come from kn held one piece of
+    right-hand sides at a time (hgp_rt_block_stats), the (bsz, M') kn never allocated."""
 
     def __init__(self, kernel, xgrids, num_obs, xblock_size=10, block_sizes=None, sig2_init=1., ell_init=.05,
                  noise2_init=1., init_Svar=.1, learn_kernel=False, learn_noise=False, dtype=torch.float,
@@ -788,6 +821,77 @@ class BlockToeplitzGP(ToeplitzInducingGP):
         if qm is None or qS is None:
             qm, qS = self.standard_variational_params()
         return block_kl_to_standard(qm, qS)
+
+    # ---- the streamed route: the batch sums without the (bsz, M') kn ---------------------------
+    # right-hand sides per piece of kn held at a time (hgp_rt_block_stats' piece_rhs); 0: its default
+    kn_piece_rhs = 0
+
+    def _streamed_solve(self, Knm, maxiter_cg, Kmm):
+        """(Kmm, d = K^-1 Knm^T by compute_kn's PCG, in place of Knm where the tensor allows), or None
+        with Knm untouched: cholesky whitening, an empty batch, a Kmm without rt_block_stats."""
+        if self.whitened_type != 'ziggy' or Knm.shape[0] == 0:
+            return None
+        if Kmm is None:
+            Kmm = self.toeplitz()
+        if not hasattr(Kmm, "rt_block_stats"):
+            return None
+        if hasattr(Kmm, "inv_matmul_") and Knm.is_contiguous() and not Knm.requires_grad \
+                and not Kmm.column.requires_grad:
+            return Kmm, Kmm.inv_matmul_(Knm, do_precond=True, maxiter=maxiter_cg, tol=1e-8)
+        return Kmm, Kmm.inv_matmul(Knm.detach(), do_precond=True, maxiter=maxiter_cg, tol=1e-8)
+
+    def streamed_predict_stats(self, Knm, maxiter_cg=50, Kmm=None):
+        """Rows (kn.qm, |kn|^2, kn^T S kn) from ToeplitzTensor.rt_block_stats (hgp_rt_block_stats, no
+        gram) on the PCG solution, with compute_kn's PCG settings; Knm is consumed."""
+        with torch.no_grad():
+            sol = self._streamed_solve(Knm, maxiter_cg, Kmm)
+            if sol is None:
+                return None
+            Kmm, d0 = sol
+            qm, qS = self.standard_variational_params()
+            dt = d0.dtype
+            return Kmm.rt_block_stats(d0, self.block_sides, qm.detach().reshape(-1).to(dt).contiguous(),
+                                      S=qS.detach().to(dt).contiguous(), gram=False,
+                                      piece_rhs=self.kn_piece_rhs)[0]
+
+    def streamed_fit_stats(self, Knm, ybatch, Knn_diag, noise_std_batch=None, maxiter_cg=10, Kmm=None):
+        """`batch_stats` of kn = R^T K^-1 Knm^T without the (bsz, M') kn, as the mean-field
+        `fit_stats`: d = K^-1 Knm^T by compute_kn's PCG in place of Knm (consumed); the three row
+        dots and the per-block grams from ToeplitzTensor.rt_block_stats (hgp_rt_block_stats, kn held
+        `kn_piece_rhs` right-hand sides at a time); a_n and bdiff_n from the dots; and, R^T being
+        linear, dm_sum = R^T (-sum_n bdiff_n d_n): hgp_meanfield_cols on d with Mp = M and one
+        single-RHS R^T."""
+        with torch.no_grad():
+            sol = self._streamed_solve(Knm, maxiter_cg, Kmm)
+            if sol is None:
+                return None
+            Kmm, d0 = sol
+            B = d0.shape[0]
+            dev, dt = d0.device, d0.dtype
+            qm, qS = self.standard_variational_params()
+            ivar, log_sd = self.noise_terms(noise_std_batch)
+            col = lambda v: torch.as_tensor(v, dtype=dt, device=dev).detach().reshape(-1).expand(B).contiguous()
+            y, iv, kd, lsd = col(ybatch), col(ivar), col(Knn_diag), col(log_sd)
+            dots, G = Kmm.rt_block_stats(d0, self.block_sides, qm.detach().reshape(-1).to(dt).contiguous(),
+                                         S=qS.detach().to(dt).contiguous(), ivar=iv, gram=True,
+                                         piece_rhs=self.kn_piece_rhs)
+            knm, knkn, knSkn = dots[:, 0], dots[:, 1], dots[:, 2]
+            an = -0.5 * iv * ((knm - y) ** 2 + kd - knkn + knSkn) - lsd - 0.5 * LN_2PI
+            bdiff = (iv * (knm - y)).contiguous()
+            if d0.is_cuda:
+                import ctypes
+                from hipgp_amd import _lib
+                p = lambda t: ctypes.c_void_p(t.data_ptr())
+                d0 = d0.contiguous()
+                M = d0.shape[1]
+                scr = torch.empty(M, dtype=dt, device=dev)      # sum_n iv_n d_nj^2: not used
+                v = torch.empty(M, dtype=dt, device=dev)
+                _lib.check(_lib.lib().hgp_meanfield_cols(_lib.dtype_code(dt), p(d0), B, M, p(iv), p(bdiff), p(scr),
+                                                         p(v), _lib.stream_ptr(dev)))
+            else:       # CPU tensors only in the host-logic tests
+                v = -(bdiff[None, :].matmul(d0)).reshape(-1)
+            dm = Kmm._matmul_by_RT(v[None, :]).reshape(-1)
+        return {"an_sum": an.sum(), "lam_sum": G, "dm_sum": dm, "n": B}
 
     # ---- natural gradient as batch sums + update (sharding-friendly) ------------------------
     def batch_stats(self, kn, ybatch, Knn_diag, noise_std_batch=None):

@@ -125,6 +125,17 @@ class ToeplitzTensor:
             raise RuntimeError("rt_fit_stats has no backward: call it under torch.no_grad() or on detached inputs")
         return self._plan.rt_fit_stats(vec, qm, qS, ivar)
 
+    def rt_block_stats(self, vec, blocks, qm, S=None, ivar=None, gram=True, piece_rhs=0):
+        """(out3 (bsz, 3), gram or None): rows (kn.qm, |kn|^2, kn^T S kn) and the per-block grams
+        sum_n ivar[n] kn_blk kn_blk^T of kn = _matmul_by_RT(vec), the sums the block family takes
+        from kn (`hipgp.py:252-256, 661-664`), streamed a piece of right-hand sides at a time
+        without the (bsz, M') tensor (hgp_rt_block_stats).  No autograd."""
+        self._check_batch()
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                           for t in (vec, qm, S, ivar, self.column)):
+            raise RuntimeError("rt_block_stats has no backward: call it under torch.no_grad() or on detached inputs")
+        return self._plan.rt_block_stats(vec, blocks, qm, S=S, ivar=ivar, gram=gram, piece_rhs=piece_rhs)
+
     def _matmul_by_R(self, vec):
         self._check_batch()
         return self._op(_lib.OP_R, vec.reshape(vec.shape[0], -1))

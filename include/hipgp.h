@@ -110,6 +110,25 @@ int hgp_rt_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, co
 int hgp_rt_fit_stats(hgp_plan* plan, const void* d, int64_t nrhs, const void* qm, const void* qS,
                      const void* ivar, void* out3, void* lam);
 
+/* The block-diagonal family's sums (hipgp.py:252-256, 661-664) without the (nrhs, M') kn = R^T d:
+ *   gram[blk] = sum_n ivar[n] kn_{n,blk} kn_{n,blk}^T   ([nblk][bs][bs], overwritten; may be NULL,
+ *               and ivar then too),
+ *   out3[n*3 + c] = (kn_n.qm, |kn_n|^2, kn_n^T S kn_n)  (S: [nblk][bs][bs], block diagonal; NULL: 0).
+ * blocks[ndim] tiles the plan's expanded grid n_a = 2 m_a - 2 under hgp_block_stats's rules (each
+ * side divides its axis, <= 128 points per block, 2-D / 3-D).  A gram entry pairs kn values of
+ * different grid rows, so this is no epilogue of R^T's last pass: R^T runs into plan scratch
+ * piece_rhs right-hand sides at a time and one kernel reads each piece once for the gram and the
+ * three dots, the gram continuing from piece to piece (one owner thread per entry and launch,
+ * launches ordered on the plan's stream: no atomics, bit-reproducible).  piece_rhs = 0:
+ * min(nrhs, max(32 Mi values / M', bs)) -- every piece re-reads and re-writes the gram, as much as
+ * bs rows of kn.  Extra memory: one piece plus 3 piece_rhs row partials per workgroup, independent
+ * of nrhs (hgp_plan_mem reports it, hgp_plan_trim frees it).  Every route of HGP_OP_RT.
+ * nrhs = 0: gram zeroed, nothing else written.  HGP_E_ARG: null plan / pointer, nrhs < 0,
+ * piece_rhs < 0; HGP_E_STATE: no column set; HGP_E_UNSUPPORTED: 1-D plans, a size-1 axis, refused
+ * block shapes. */
+int hgp_rt_block_stats(hgp_plan* plan, const void* d, int64_t nrhs, const int64_t* blocks, int64_t piece_rhs,
+                       const void* qm, const void* S, const void* ivar, void* out3, void* gram);
+
 /* Batched PCG, exactly the recurrence of conj_grad2 (cg.py:44-80) for layout ROWS
  * (b,x:(nrhs,M)) and conj_grad (cg.py:5-41) for layout COLS (b,x:(M,nrhs)): A = K,
  * preconditioner C^-1 if use_precond, x0 = 0, per-RHS alpha/beta, stop when ALL
