@@ -33,7 +33,7 @@ EXPORTS = (
     "hgp_slab_info", "hgp_slab_pass", "hgp_plan_mem", "hgp_plan_trim",
     "hgp_slab_pass_ex", "hgp_slab_cg_xr", "hgp_slab_cg_check", "hgp_slab_cg_p",
     "hgp_meanfield_rowdots", "hgp_meanfield_cols", "hgp_rt_stats", "hgp_rt_fit_stats",
-    "hgp_rt_block_stats",
+    "hgp_rt_block_stats", "hgp_kuf_grid_grad", "hgp_kuf_semi_mc_grad", "hgp_kuf_semi_sqexp_grad",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -78,6 +78,10 @@ def lib():
         "hgp_kuf_grid": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp]),
         "hgp_kuf_semi_mc": (i32, [i32, i32, dbl, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, i32, vp, vp, vp]),
         "hgp_kuf_semi_sqexp": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp]),
+        "hgp_kuf_grid_grad": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp, vp]),
+        "hgp_kuf_semi_mc_grad": (i32, [i32, i32, dbl, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, i32, vp, vp, vp,
+                                       vp]),
+        "hgp_kuf_semi_sqexp_grad": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp, vp]),
         "hgp_knn_doubly_diag": (i32, [i32, i32, vp, i64, dbl, dbl, vp, i32, vp, vp]),
         "hgp_meanfield_stats": (i32, [i32, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hgp_meanfield_rowdots": (i32, [i32, vp, i64, i64, vp, vp, vp, vp]),

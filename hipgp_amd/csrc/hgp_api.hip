@@ -2222,6 +2222,52 @@ int hgp_kuf_semi_sqexp(int dtype, int ndim, const int64_t* m, const void* const*
   return 0;
 }
 
+// the checks the three (sig2, ell) backward entries share; all before any HIP call
+static int check_grad_args(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                           int64_t nobs, const void* g, const void* grad2) {
+  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
+  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
+  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_GNEITING) return fail(HGP_E_ARG, "bad kernel kind");
+  if (grad2 == nullptr) return fail(HGP_E_ARG, "grad2 is null");
+  if (nobs < 0 || (nobs > 0 && (x == nullptr || g == nullptr))) return fail(HGP_E_ARG, "bad x/g/nobs");
+  for (int a = 0; a < ndim; ++a)
+    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
+  if (kind == HGP_KERN_GNEITING)
+    return fail(HGP_E_UNSUPPORTED, "no hyper-parameter gradient for the Gneiting kernel (the reference's is NaN at r = 0)");
+  return 0;
+}
+
+int hgp_kuf_grid_grad(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                      int64_t nobs, double sig2, double ell, const void* g, void* grad2, void* hip_stream) {
+  HGP_TRY(check_grad_args(dtype, kind, ndim, m, grids, x, nobs, g, grad2));
+  hipError_t e = kuf_grad(dtype, 0, kind, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, g, grad2,
+                          reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_grad: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_mc_grad(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
+                         const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u,
+                         const void* g, void* grad2, void* hip_stream) {
+  (void)kparam;   // Gneiting's alpha: that kernel is refused below
+  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
+  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
+  HGP_TRY(check_grad_args(dtype, kind, ndim, m, grids, x, nobs, g, grad2));
+  hipError_t e = kuf_grad(dtype, 1, kind, ndim, m, grids, x, nobs, sig2, ell, npts, u, g, grad2,
+                          reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_grad: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_sqexp_grad(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                            int64_t nobs, double sig2, double ell, const void* g, void* grad2, void* hip_stream) {
+  HGP_TRY(check_grad_args(dtype, HGP_KERN_SQEXP, ndim, m, grids, x, nobs, g, grad2));
+  hipError_t e = kuf_grad(dtype, 2, HGP_KERN_SQEXP, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, g, grad2,
+                          reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_grad: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_knn_doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* table,
                         int N, void* out, void* hip_stream) {
   if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");

@@ -308,4 +308,330 @@ hipError_t kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void*
   return hipGetLastError();
 }
 
+// ---- backward of the three cross covariances with respect to (sig2, ell) ---------------------
+// With G the upstream gradient (nobs, M) the hyper-parameter gradients are two scalar sums
+//   grad2[0] = sum_nj G[n,j] dK[n,j]/dsig2,   grad2[1] = sum_nj G[n,j] dK[n,j]/dell
+// (the autograd of kernels.py:73-79, 145-158, 19-39, 80-85, 223-237 builds and keeps the
+// (B, M, D) difference, its square, the distance and the exponential for them).  K is recomputed
+// per element with the forward's arithmetic, so nothing is stored between forward and backward.
+//
+// Block map: the forward's tiles (n, outer index o, chunk of the last axis), numbered as the
+// forward's blockIdx; at most KUF_GRAD_BLOCKS blocks, block b takes tiles b, b + nblk, ... in
+// that order.  Reduction, all in fp64 whatever the tensor dtype and with no atomics, so the
+// result is the same bits on every call: a thread adds its terms in tile order; the 64 lanes of
+// a wave by the xor butterfly (32, 16, ..., 1); the 4 waves of a block in wave order through
+// LDS; one (d/dsig2, d/dell) pair per block to `part`; k_kuf_grad_finish sums the pairs
+// (thread t takes pairs t, t + 256, ..., then the same wave and block steps) and writes grad2.
+//
+// Every kernel is K = sig2 * k0, so dK/dsig2 = k0: the kernel value without the sig2 factor.
+// dK/dell = sig2 * kl with, for r = |x - u| and s as in kern_eval:
+//   SqExp       k0 = e^{-s/2}, s = r^2/ell^2, ds/dell = -2 s/ell     -> kl = k0 s / ell
+//   Matern 1/2  k0 = e^{-r/ell}                                      -> kl = k0 r / ell^2
+//   Matern 3/2  k0 = (1 + dp) e^{-dp}, dp = sqrt3 r/ell: dk0/ddp = -dp e^{-dp},
+//               ddp/dell = -dp/ell                                   -> kl = dp^2 e^{-dp} / ell
+//   Matern 5/2  k0 = (1 + dp + dp^2/3) e^{-dp}, dp = sqrt5 r/ell:
+//               dk0/ddp = -dp (1 + dp) e^{-dp} / 3                   -> kl = dp^2 (1 + dp) e^{-dp} / (3 ell)
+// all finite and zero at r = 0 (torch's autograd agrees: the squared distance carries no graph
+// when x does not require grad, so sqrt'(0) is never multiplied in).
+constexpr int KUF_GRAD_BLOCKS = 2048;
+
+template <typename T>
+__device__ __forceinline__ void kern_grad_terms(int kind, T s, T ell, T& k0, T& kl) {
+  if (kind == HGP_KERN_SQEXP) {
+    k0 = exp(-s / (T)2);
+    kl = k0 * s / ell;
+    return;
+  }
+  const T r = sqrt(s);
+  if (kind == HGP_KERN_MATERN12) {
+    k0 = exp(-r / ell);
+    kl = k0 * r / (ell * ell);
+    return;
+  }
+  if (kind == HGP_KERN_MATERN32) {
+    const T dp = (T)1.7320508075688772935 * r / ell;
+    const T e = exp(-dp);
+    k0 = ((T)1 + dp) * e;
+    kl = dp * dp * e / ell;
+    return;
+  }
+  const T dp = (T)2.2360679774997896964 * r / ell;       // Matern 5/2
+  const T e = exp(-dp);
+  k0 = ((T)1 + dp + ((T)5 / (T)3) * s / (ell * ell)) * e;
+  kl = dp * dp * ((T)1 + dp) * e / ((T)3 * ell);
+}
+
+// wave (xor butterfly) then block (wave order) sum of a pair; thread 0 / 1 of the block write it
+__device__ __forceinline__ void kuf_block_sum2(double a0, double a1, double* __restrict__ pair) {
+  __shared__ double red[2][KUF_THREADS / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    a0 += __shfl_xor(a0, off, 64);
+    a1 += __shfl_xor(a1, off, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[0][w] = a0; red[1][w] = a1; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double s = 0;
+    for (int k = 0; k < KUF_THREADS / 64; ++k) s += red[threadIdx.x][k];
+    pair[threadIdx.x] = s;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid_grad(KufGrid g, const T* __restrict__ x, int kind, T ell,
+                                                              const T* __restrict__ gup, int64_t ntile,
+                                                              double* __restrict__ part) {
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  const int64_t nchunk = (inner + KUF_CHUNK - 1) / KUF_CHUNK;
+  int64_t outer = 1;
+  for (int a = 0; a < d - 1; ++a) outer *= g.m[a];
+  const bool sq = scaled_dist(kind);
+  const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
+  double a0 = 0, a1 = 0;
+  for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+    const int64_t chunk = t % nchunk;
+    const int64_t rest = t / nchunk;
+    const int64_t o = rest % outer;
+    const int64_t n = rest / outer;                         // < nobs: t < ntile = nobs * outer * nchunk
+    auto sqd = [&](int a, int64_t ia) -> T {
+      T dv = x[n * d + a] - reinterpret_cast<const T*>(g.g[a])[ia];
+      if (sq) dv = dv / ell;
+      return dv * dv;
+    };
+    T so = 0;
+    if (d == 2) so = sqd(0, o);
+    if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
+    const T xl = x[n * d + d - 1];
+    const T* grow = gup + (n * outer + o) * inner;
+#pragma unroll
+    for (int k = 0; k < KUF_PER_THREAD; ++k) {
+      const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
+      if (i < inner) {
+        T dv = xl - gl[i];
+        if (sq) dv = dv / ell;
+        const T s = (d == 1) ? dv * dv : so + dv * dv;
+        T k0, kl;
+        kern_grad_terms<T>(kind, s, ell, k0, kl);
+        const T gv = grow[i];
+        a0 += (double)(gv * k0);
+        a1 += (double)(gv * kl);
+      }
+    }
+  }
+  kuf_block_sum2(a0, a1, part + 2 * (int64_t)blockIdx.x);
+}
+
+// k_semi_mc is |x_n| mean_a k(u_j, alpha_a x_n) and neither |x_n| nor alpha_a depends on the
+// hyper-parameters, so both derivatives are |x_n| mean_a of the point terms at the samples.
+template <typename T>
+__global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_mc_grad(KufGrid g, const T* __restrict__ x, int kind, T ell,
+                                                                 int npts, const T* __restrict__ u,
+                                                                 const T* __restrict__ gup, int64_t ntile,
+                                                                 double* __restrict__ part) {
+  __shared__ T so_s[SEMI_MAX_NPTS];
+  __shared__ T xl_s[SEMI_MAX_NPTS];
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  const int64_t nchunk = (inner + KUF_CHUNK - 1) / KUF_CHUNK;
+  int64_t outer = 1;
+  for (int a = 0; a < d - 1; ++a) outer *= g.m[a];
+  const bool sq = scaled_dist(kind);
+  const T uoff = u[0] * (T)(1.0 / (double)npts);
+  const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
+  double a0 = 0, a1 = 0;
+  for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {   // the same trip count for every thread
+    const int64_t chunk = t % nchunk;
+    const int64_t rest = t / nchunk;
+    const int64_t o = rest % outer;
+    const int64_t n = rest / outer;
+    __syncthreads();                                          // the last tile's readers are done
+    for (int a = threadIdx.x; a < npts; a += KUF_THREADS) {
+      const T al = (T)a / (T)npts + uoff;
+      auto sqd = [&](int ax, int64_t ia) -> T {
+        T dv = reinterpret_cast<const T*>(g.g[ax])[ia] - x[n * d + ax] * al;
+        if (sq) dv = dv / ell;
+        return dv * dv;
+      };
+      T so = 0;
+      if (d == 2) so = sqd(0, o);
+      if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
+      so_s[a] = so;
+      xl_s[a] = x[n * d + d - 1] * al;
+    }
+    __syncthreads();
+    T xn2 = 0;
+    for (int ax = 0; ax < d; ++ax) xn2 += x[n * d + ax] * x[n * d + ax];
+    const T dist = sqrt(xn2);
+    const T* grow = gup + (n * outer + o) * inner;
+#pragma unroll
+    for (int k = 0; k < KUF_PER_THREAD; ++k) {
+      const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
+      if (i < inner) {
+        const T ui = gl[i];
+        T acc0 = 0, accl = 0;
+        for (int a = 0; a < npts; ++a) {
+          T dv = ui - xl_s[a];
+          if (sq) dv = dv / ell;
+          const T s = (d == 1) ? dv * dv : so_s[a] + dv * dv;
+          T k0, kl;
+          kern_grad_terms<T>(kind, s, ell, k0, kl);
+          acc0 += k0;
+          accl += kl;
+        }
+        const T gv = grow[i];
+        a0 += (double)(gv * (acc0 / (T)npts * dist));
+        a1 += (double)(gv * (accl / (T)npts * dist));
+      }
+    }
+  }
+  kuf_block_sum2(a0, a1, part + 2 * (int64_t)blockIdx.x);
+}
+
+// Analytic SqExp line integral: with Sinv = I / ell^2 the forward's terms are
+//   a = |x|^2/ell^2, b = x.u/ell^2, c = |u|^2/ell^2,  loc = b/a = x.u/|x|^2   (no ell in it),
+//   E = b^2/(2a) - c/2 = -q/(2 ell^2),  q = c ell^2 - b^2 ell^2/a = |u|^2 - (x.u)^2/|x|^2
+//   (the squared distance of u from the line), scale = sqrt(1/a) = ell/|x|,
+//   za = (1 - loc)/(scale sqrt2) = A/ell, zb = -loc/(scale sqrt2) = B0/ell,
+//   A = (1 - loc)|x|/sqrt2, B0 = -loc |x|/sqrt2,
+//   K = sig2 k0,  k0 = e^E sqrt(2 pi) scale (erf(za) - erf(zb))/2 |x|
+//                    = sqrt(2 pi) ell e^{-q/(2 ell^2)} (erf(A/ell) - erf(B0/ell))/2.
+// Differentiating the three factors that hold ell:
+//   d(ell)/dell                 -> k0/ell
+//   d e^{-q/(2 ell^2)}/dell     -> k0 q/ell^3 = k0 (-2E)/ell
+//   d erf(A/ell)/dell = -(2/sqrt pi) e^{-za^2} A/ell^2, likewise B0:
+//     sqrt(2 pi) ell e^E (1/2)(2/sqrt pi)(-za e^{-za^2} + zb e^{-zb^2})/ell
+//                               -> -sqrt2 e^E (za e^{-za^2} - zb e^{-zb^2})
+//   kl = k0 (1 - 2E)/ell - sqrt2 e^E (za e^{-za^2} - zb e^{-zb^2}).
+// a, b, c, loc, E, za, zb are formed exactly as in k_kuf_semi_sqexp.
+template <typename T>
+__global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_sqexp_grad(KufGrid g, const T* __restrict__ x, T ell,
+                                                                    const T* __restrict__ gup, int64_t ntile,
+                                                                    double* __restrict__ part) {
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  const int64_t nchunk = (inner + KUF_CHUNK - 1) / KUF_CHUNK;
+  int64_t outer = 1;
+  for (int a = 0; a < d - 1; ++a) outer *= g.m[a];
+  const T sinv = (T)1 / (ell * ell);
+  const T sqrt2 = (T)1.4142135623730950488, sqrt2pi = (T)2.5066282746310005024;
+  const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
+  double a0 = 0, a1 = 0;
+  for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+    const int64_t chunk = t % nchunk;
+    const int64_t rest = t / nchunk;
+    const int64_t o = rest % outer;
+    const int64_t n = rest / outer;
+    T xs[3], ua[3];
+    T av = 0, xn2 = 0;
+    int64_t oi[2] = {0, 0};
+    if (d == 2) oi[0] = o;
+    if (d == 3) { oi[0] = o / g.m[1]; oi[1] = o % g.m[1]; }
+    for (int ax = 0; ax < d; ++ax) {
+      const T xv = x[n * d + ax];
+      xs[ax] = xv * sinv;
+      av += xs[ax] * xv;
+      xn2 += xv * xv;
+      if (ax < d - 1) ua[ax] = reinterpret_cast<const T*>(g.g[ax])[oi[ax]];
+    }
+    T bo = 0, co = 0;
+    for (int ax = 0; ax < d - 1; ++ax) {
+      bo += xs[ax] * ua[ax];
+      co += (ua[ax] * sinv) * ua[ax];
+    }
+    const T xdist = sqrt(xn2);
+    const T scale = sqrt((T)1 / av);
+    const T* grow = gup + (n * outer + o) * inner;
+#pragma unroll
+    for (int k = 0; k < KUF_PER_THREAD; ++k) {
+      const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
+      if (i < inner) {
+        const T ui = gl[i];
+        const T b = (d == 1) ? xs[0] * ui : bo + xs[d - 1] * ui;
+        const T c = (d == 1) ? (ui * sinv) * ui : co + (ui * sinv) * ui;
+        const T loc = b / av;
+        const T E = (b * b) / ((T)2 * av) - c / (T)2;
+        const T eE = exp(E);
+        const T za = ((T)1 - loc) / (scale * sqrt2);
+        const T zb = ((T)0 - loc) / (scale * sqrt2);
+        const T ca = (T)0.5 * ((T)1 + erf(za));
+        const T cb = (T)0.5 * ((T)1 + erf(zb));
+        const T k0 = eE * sqrt2pi * scale * (ca - cb) * xdist;
+        const T kl = k0 * ((T)1 - (T)2 * E) / ell - sqrt2 * eE * (za * exp(-za * za) - zb * exp(-zb * zb));
+        const T gv = grow[i];
+        a0 += (double)(gv * k0);
+        a1 += (double)(gv * kl);
+      }
+    }
+  }
+  kuf_block_sum2(a0, a1, part + 2 * (int64_t)blockIdx.x);
+}
+
+// the pairs of all blocks in a fixed order (fp64), times sig2 for d/dell, in the tensor dtype
+template <typename T>
+__global__ __launch_bounds__(KUF_THREADS) void k_kuf_grad_finish(const double* __restrict__ part, int np,
+                                                                double sig2, T* __restrict__ grad2) {
+  __shared__ double tot[2];
+  double a0 = 0, a1 = 0;
+  for (int p = threadIdx.x; p < np; p += KUF_THREADS) {
+    a0 += part[2 * p];
+    a1 += part[2 * p + 1];
+  }
+  kuf_block_sum2(a0, a1, tot);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    grad2[0] = (T)tot[0];
+    grad2[1] = (T)(sig2 * tot[1]);
+  }
+}
+
+// mode: 0 point observations, 1 semi-mc, 2 semi-sqexp
+template <typename T>
+static hipError_t kuf_grad_t(int mode, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                             int64_t nobs, double sig2, double ell, int npts, const void* u, const void* gup,
+                             void* grad2, hipStream_t s) {
+  if (nobs == 0) return hipMemsetAsync(grad2, 0, 2 * sizeof(T), s);
+  KufGrid g{};
+  g.d = ndim;
+  int64_t outer = 1;
+  for (int a = 0; a < ndim; ++a) {
+    g.m[a] = m[a];
+    g.g[a] = grids[a];
+    if (a < ndim - 1) outer *= m[a];
+  }
+  const int64_t nchunk = (m[ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK;
+  const int64_t ntile = nobs * outer * nchunk;
+  const int nblk = (int)(ntile < KUF_GRAD_BLOCKS ? ntile : KUF_GRAD_BLOCKS);
+  double* part = nullptr;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)nblk * 2 * sizeof(double), s);
+  if (e != hipSuccess) return e;
+  const T* xt = reinterpret_cast<const T*>(x);
+  const T* gt = reinterpret_cast<const T*>(gup);
+  if (mode == 0)
+    hipLaunchKernelGGL((k_kuf_grid_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, kind, (T)ell, gt,
+                       ntile, part);
+  else if (mode == 1)
+    hipLaunchKernelGGL((k_kuf_semi_mc_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, kind, (T)ell,
+                       npts, reinterpret_cast<const T*>(u), gt, ntile, part);
+  else
+    hipLaunchKernelGGL((k_kuf_semi_sqexp_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, (T)ell, gt,
+                       ntile, part);
+  hipLaunchKernelGGL((k_kuf_grad_finish<T>), dim3(1), dim3(KUF_THREADS), 0, s, part, nblk, sig2,
+                     reinterpret_cast<T*>(grad2));
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipFreeAsync(part, s);
+}
+
+// launcher behind hgp_kuf_grid_grad / hgp_kuf_semi_mc_grad / hgp_kuf_semi_sqexp_grad
+hipError_t kuf_grad(int dtype, int mode, int kind, int ndim, const int64_t* m, const void* const* grids,
+                    const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* gup,
+                    void* grad2, hipStream_t s) {
+  if (dtype == HGP_F32)
+    return kuf_grad_t<float>(mode, kind, ndim, m, grids, x, nobs, sig2, ell, npts, u, gup, grad2, s);
+  return kuf_grad_t<double>(mode, kind, ndim, m, grids, x, nobs, sig2, ell, npts, u, gup, grad2, s);
+}
+
 }  // namespace hgp

@@ -6,6 +6,11 @@ observations (hgp_kuf_semi_mc / hgp_kuf_semi_sqexp / hgp_knn_doubly_diag).
 kernel straight into the (B, M) layout the PCG reads.  Used when the kernel is SqExp or
 Matern(nu in {1/2, 3/2, 5/2}) with a scalar length scale and no gradient is needed; other
 kernels (or kernel-hyper-parameter learning) evaluate the torch kernel on the device.
+
+Kernel-hyper-parameter learning has fused twins, `kuf_grid_ad` / `kuf_semi_mc_ad` /
+`kuf_semi_sqexp_ad`: the same forward, and the gradient with respect to (sig2, ell) by
+hgp_kuf_*_grad, which recomputes K instead of keeping the broadcast for autograd
+(`SviGP._make_grams` uses them when the model's `kuf_grad` knob is on).
 """
 import ctypes
 
@@ -140,3 +145,126 @@ def knn_doubly_diag(table, x, params):
                                     s2, el, ctypes.c_void_p(tab.data_ptr()), tab.shape[1],
                                     ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
     return out
+
+
+# ---- the same cross covariances with a graph to (sig2, ell): kernel hyper-parameter learning ----
+# The forward is the fused kernel above; the backward is two scalar sums over (nobs, M) with K
+# recomputed in the kernel (hgp_kuf_*_grad), so nothing of the (nobs, M, D) broadcast that torch's
+# autograd of `kernels.py:73-79, 145-158, 19-39, 80-85, 223-237` saves is ever allocated.
+
+class _KufAD(torch.autograd.Function):
+    """out = fwd(sig2, ell) (the plain fused forward on the detached scalars); the backward hands
+    the upstream gradient to bwd(sig2, ell, G) -> grad2 = (sum G dK/dsig2, sum G dK/dell).  Only
+    the detached scalars are kept on ctx; x, the grids and the MC offset live in the closures."""
+
+    @staticmethod
+    def forward(ctx, sig2, ell, fwd, bwd):
+        ctx.s2, ctx.el, ctx.bwd = _scalar(sig2), _scalar(ell), bwd
+        ctx.like = [(p.shape, p.dtype) if torch.is_tensor(p) else None for p in (sig2, ell)]
+        return fwd(ctx.s2, ctx.el)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        grad2 = ctx.bwd(ctx.s2, ctx.el, G.contiguous())
+        out = [grad2[i].to(ctx.like[i][1]).reshape(ctx.like[i][0]) if ctx.needs_input_grad[i] else None
+               for i in range(2)]
+        return out[0], out[1], None, None
+
+
+def _ad_route(kernel, xgrids, x, params):
+    """None: the `_ad` function declines (caller evaluates the torch kernel); False: no
+    hyper-parameter gradient is asked for (the plain forward serves); else the HGP_KERN_* code."""
+    if xgrids is None or not torch.is_tensor(x) or x.requires_grad and torch.is_grad_enabled():
+        return None
+    kind = kernel_kind(kernel)                       # no Gneiting: its gradient is NaN at r = 0
+    if kind is None or x.device.type != "cuda" or x.dim() != 2 or x.shape[1] != len(xgrids):
+        return None
+    if x.dtype not in (torch.float32, torch.float64) or len(xgrids) > 3:
+        return None
+    if any(torch.is_tensor(p) and p.numel() != 1 for p in params):
+        return None
+    if not (torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in params)):
+        return False
+    return kind
+
+
+def _grad_call(entry, x, G, *args):
+    """Run one hgp_kuf_*_grad entry: args are everything between dtype and g."""
+    grad2 = torch.empty(2, dtype=x.dtype, device=x.device)
+    check(entry(_lib.dtype_code(x.dtype), *args, ctypes.c_void_p(G.data_ptr()), ctypes.c_void_p(grad2.data_ptr()),
+                _lib.stream_ptr(x.device)))
+    return grad2
+
+
+def _ad_inputs(xgrids, x):
+    grids = [g.to(device=x.device, dtype=x.dtype).contiguous() for g in xgrids]
+    return grids, x.detach().contiguous()
+
+
+def kuf_grid_ad(kernel, xgrids, x, params):
+    """`kuf_grid` that carries the autograd graph to sig2 / ell: the same forward values, the
+    backward by hgp_kuf_grid_grad.  None when it does not apply: x requires grad, a non-scalar
+    ell, Gneiting or another kernel without a fused forward, a CPU tensor, more than 3 dims."""
+    kind = _ad_route(kernel, xgrids, x, params)
+    if kind is None:
+        return None
+    if kind is False:
+        return kuf_grid(kernel, xgrids, x, params)
+    grids, xc = _ad_inputs(xgrids, x)
+
+    def bwd(s2, el, G):
+        m, ptrs = _grid_ptrs(grids)
+        return _grad_call(lib().hgp_kuf_grid_grad, xc, G, kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
+                          xc.shape[0], s2, el)
+    return _KufAD.apply(params[0], params[1], lambda s2, el: kuf_grid(kernel, grids, xc, (s2, el)), bwd)
+
+
+def kuf_semi_mc_ad(kernel, xgrids, x, params, npts, u=None):
+    """`kuf_semi_mc` with the graph to sig2 / ell (backward: hgp_kuf_semi_mc_grad on the offset
+    draw the forward used; drawn here exactly as `kuf_semi_mc` draws it when not given)."""
+    kind = _ad_route(kernel, xgrids, x, params)
+    if kind is None:
+        return None
+    if kind is False:
+        return kuf_semi_mc(kernel, xgrids, x, params, npts, u=u)
+    grids, xc = _ad_inputs(xgrids, x)
+    if u is None:
+        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
+    uc = u.detach().to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
+
+    def bwd(s2, el, G):
+        m, ptrs = _grid_ptrs(grids)
+        return _grad_call(lib().hgp_kuf_semi_mc_grad, xc, G, kind, 1., len(grids), m, ptrs,
+                          ctypes.c_void_p(xc.data_ptr()), xc.shape[0], s2, el, int(npts),
+                          ctypes.c_void_p(uc.data_ptr()))
+    return _KufAD.apply(params[0], params[1],
+                        lambda s2, el: kuf_semi_mc(kernel, grids, xc, (s2, el), npts, u=uc), bwd)
+
+
+def kuf_semi_sqexp_ad(kernel, xgrids, x, params):
+    """`kuf_semi_sqexp` with the graph to sig2 / ell (backward: hgp_kuf_semi_sqexp_grad)."""
+    kind = _ad_route(kernel, xgrids, x, params)
+    if kind is None or kind is not False and kind != _lib.KERN_SQEXP:
+        return None
+    if kind is False:
+        return kuf_semi_sqexp(kernel, xgrids, x, params)
+    grids, xc = _ad_inputs(xgrids, x)
+
+    def bwd(s2, el, G):
+        m, ptrs = _grid_ptrs(grids)
+        return _grad_call(lib().hgp_kuf_semi_sqexp_grad, xc, G, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
+                          xc.shape[0], s2, el)
+    return _KufAD.apply(params[0], params[1], lambda s2, el: kuf_semi_sqexp(kernel, grids, xc, (s2, el)), bwd)
+
+
+def knn_doubly_diag_ad(table, x, params):
+    """`knn_doubly_diag` in plain torch, the reference's own formula
+    (`KernelDoublyDiagInterpolator.forward` `kernels.py:199-218`), so that Knn_diag carries the
+    graph to sig2 / ell; nobs values, any device.  table: (3, N) = distance grid, knn, slopes."""
+    sig2, ell = params
+    grid, knn, slopes = table.to(device=x.device, dtype=x.dtype)
+    dists = torch.sqrt(torch.sum((x / ell) ** 2, dim=-1))
+    lo = torch.sum(dists[:, None] > grid, -1) - 1            # -1 wraps to the last entry, as the reference
+    ivals = knn[lo] + slopes[lo] * (dists - grid[lo])
+    return ell * ell * sig2 * ivals

@@ -231,7 +231,12 @@ class ToeplitzInducingGP(SviGP):
         streamed=True is the block family's route to the same end (`streamed_fit_stats`,
         hgp_rt_block_stats: kn held one piece of right-hand sides at a time), tried first and under
         the same condition; a family without it proceeds as if the keyword were off.  None reads
-        HGP_BLOCK_STREAMED (default off)."""
+        HGP_BLOCK_STREAMED (default off).
+
+        With learn_kernel the returned ELBO carries the graph through Knm; the model attribute
+        `kuf_grad` (None reads HGP_KUF_GRAD, default off) makes that graph the fused Kuf forward
+        and backward of `hipgp_amd.kuf` (`SviGP._make_grams`) instead of torch's (B, M, D)
+        broadcast and the intermediates autograd keeps of it."""
         assert self.parameterization == 'expectation-family', \
             "need parameterization=expectation-family when performing natural gradient descent"
         if fused is None:

@@ -35,6 +35,18 @@ class SviGP(nn.Module):
     def __init__(self):
         super().__init__()
         self.pred_scale_factor = 1.
+        # the fused Kuf backward for kernel hyper-parameter learning (see _make_grams):
+        # True / False, or None to read HGP_KUF_GRAD (default off)
+        self.kuf_grad = None
+
+    def _kuf_grad_route(self, params):
+        """True when `_make_grams` should try the `_ad` kernels of `hipgp_amd.kuf`: the knob
+        `kuf_grad` (None: env HGP_KUF_GRAD, default off) is on and a kernel hyper-parameter
+        requires grad."""
+        on = getattr(self, "kuf_grad", None)
+        if on is None:
+            on = os.environ.get("HGP_KUF_GRAD", "0") not in ("", "0")
+        return bool(on) and torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in params)
 
     def torch(self, arr):
         """numpy -> tensor of the model dtype; tensors must already have it (`svi_gp.py:24-32`).
@@ -70,7 +82,16 @@ class SviGP(nn.Module):
         Not in the reference (sharded fits): mc_offset -- the MC line-integral estimator's offset
         draw to use instead of drawing one here (`hipgp_amd.dist.shared_mc_offset`); grid_rows =
         (a, b) -- only the Knm columns of the grid's axis-0 rows [a, b) (a grid-block slab,
-        `hipgp_amd.slab.SlabFit`: columns [a * M / m0, b * M / m0) of the full Knm)."""
+        `hipgp_amd.slab.SlabFit`: columns [a * M / m0, b * M / m0) of the full Knm).
+
+        Kernel hyper-parameter learning (sig2 or ell requires grad): the fused kernels decline and
+        Knm is the torch kernel's (B, M, D) broadcast, which autograd also keeps for the backward.
+        With the knob `kuf_grad` on (attribute; None reads HGP_KUF_GRAD, default off) the `_ad`
+        functions of `hipgp_amd.kuf` are tried first: the same fused forward, and a backward of two
+        scalar sums that recomputes K (hgp_kuf_*_grad), so Knm is the only (B, M) array; for
+        line-integral observations Knn_diag then carries its graph too (`knn_doubly_diag_ad`).
+        Where an `_ad` function does not apply (Gneiting, a non-scalar ell, no grid, ...) the torch
+        kernel is evaluated as before."""
         params = self.get_kernel_params()
         grids, xinduce = getattr(self, "xgrids", None), self.xinduce
         if grid_rows is not None:
@@ -83,8 +104,11 @@ class SviGP(nn.Module):
                                                grids, xinduce, mc_offset)
         Knm = None
         if grids is not None:
-            from hipgp_amd.kuf import kuf_grid
-            Knm = kuf_grid(self.kernel, grids, xbatch, params)          # fused HIP kernel
+            from hipgp_amd.kuf import kuf_grid, kuf_grid_ad
+            if self._kuf_grad_route(params):
+                Knm = kuf_grid_ad(self.kernel, grids, xbatch, params)   # fused forward and backward
+            else:
+                Knm = kuf_grid(self.kernel, grids, xbatch, params)      # fused HIP kernel
         if Knm is None:
             Knm = self.kernel(xbatch, xinduce, params)
         return Knm, self.kernel.diag(xbatch, params)
@@ -96,18 +120,24 @@ class SviGP(nn.Module):
         from hipgp_amd import kuf
         if xinduce is None:
             grids, xinduce = getattr(self, "xgrids", None), self.xinduce
+        ad = self._kuf_grad_route(params)       # hyper-parameter learning with the kuf_grad knob on
+        semi_sqexp = kuf.kuf_semi_sqexp_ad if ad else kuf.kuf_semi_sqexp
+        semi_mc = kuf.kuf_semi_mc_ad if ad else kuf.kuf_semi_mc
         if estimator == "analytic":
-            Knm = kuf.kuf_semi_sqexp(self.kernel, grids, xbatch, params) if grids is not None else None
+            Knm = semi_sqexp(self.kernel, grids, xbatch, params) if grids is not None else None
             if Knm is None:
                 Knm = self.kernel.k_semi(xinduce, xbatch, params).transpose(0, 1)
         elif estimator == "mc-biased":
-            Knm = kuf.kuf_semi_mc(self.kernel, grids, xbatch, params, samps, u=mc_offset) if grids is not None else None
+            Knm = semi_mc(self.kernel, grids, xbatch, params, samps, u=mc_offset) if grids is not None else None
             if Knm is None:
                 Knm = self.kernel.k_semi_mc(xinduce, xbatch, params, npts=samps, u=mc_offset).transpose(0, 1)
         elif estimator == "numerical":
             Knm = self.kernel.k_semi_num(xinduce, xbatch, params).transpose(0, 1)
         else:
             raise NotImplementedError
+        if ad:      # the table interpolation in torch: hgp_knn_doubly_diag takes detached scalars
+            table = self.kernel.diag_interp.table(xbatch.device, xbatch.dtype)
+            return Knm, kuf.knn_doubly_diag_ad(table, xbatch, params)
         return Knm, self.kernel.k_doubly_diag(xbatch, params)
 
     def batch_predict(self, x, batch_size, verbose=True, **kwargs):

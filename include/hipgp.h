@@ -264,6 +264,37 @@ int hgp_kuf_semi_sqexp(int dtype, int ndim, const int64_t* m, const void* const*
                        const void* x, int64_t nobs, double sig2, double ell, void* out,
                        void* hip_stream);
 
+/* Backward of hgp_kuf_grid with respect to the two kernel hyper-parameters: with g (nobs, M)
+ * the upstream gradient, laid out as the forward's out,
+ *   grad2[0] = sum_{n,j} g[n,j] dK[n,j]/dsig2,   grad2[1] = sum_{n,j} g[n,j] dK[n,j]/dell
+ * (device, 2 values of dtype, ordered on hip_stream).  K is recomputed from x and the grids with
+ * the forward's arithmetic, so nothing of the forward is kept: this replaces torch's autograd of
+ * kernels.py:73-79, 145-158, which saves the (nobs, M, ndim) difference, its square, the
+ * distance and the exponential.  kind: HGP_KERN_SQEXP / HGP_KERN_MATERN{12,32,52};
+ * HGP_KERN_GNEITING returns HGP_E_UNSUPPORTED (the reference's own gradient is NaN at a
+ * coincident point).  Sums in fp64 in a fixed order, no atomics: the same bits on every call.
+ * nobs = 0: two zeros.  HGP_E_ARG (before any HIP call): null pointer, bad dtype / kind / ndim,
+ * nobs < 0.  Scratch: at most 2048 fp64 pairs, stream-ordered (hipMallocAsync). */
+int hgp_kuf_grid_grad(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                      const void* x, int64_t nobs, double sig2, double ell,
+                      const void* g, void* grad2, void* hip_stream);
+
+/* The same two sums for hgp_kuf_semi_mc (the autograd of Kernel.k_semi_mc, kernels.py:19-39,
+ * through its (M, nobs * npts, ndim) broadcast): |x_n| mean_a of the point derivatives at the
+ * sample points alpha_a x_n.  u: the offset draw the forward used.  kparam is ignored (Gneiting
+ * is refused as above).  1 <= npts <= 1024 else HGP_E_ARG. */
+int hgp_kuf_semi_mc_grad(int dtype, int kind, double kparam, int ndim, const int64_t* m,
+                         const void* const* grids, const void* x, int64_t nobs,
+                         double sig2, double ell, int npts, const void* u,
+                         const void* g, void* grad2, void* hip_stream);
+
+/* The same two sums for hgp_kuf_semi_sqexp (the autograd of SqExp.k_semi ->
+ * semi_integrated_sqe, kernels.py:80-85, 223-237), SqExp only like its forward: the
+ * closed-form derivative of the forward's own expression (NaN for |x_n| = 0, as the forward). */
+int hgp_kuf_semi_sqexp_grad(int dtype, int ndim, const int64_t* m, const void* const* grids,
+                            const void* x, int64_t nobs, double sig2, double ell,
+                            const void* g, void* grad2, void* hip_stream);
+
 /* Doubly-integrated diagonal Knn_diag by table interpolation,
  * KernelDoublyDiagInterpolator.forward (kernels.py:200-220): table = device array of 3*N
  * values in dtype (distance grid, knn, slopes: the reference's float32 table), x: (nobs,
