@@ -11,41 +11,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/hipgp.h"
+#include "hgp_kuf_eval.hpp"   // KufGrid, scaled_dist, kern_eval: shared with hgp_kuf_mv.hip
 
 namespace hgp {
 
 constexpr int KUF_THREADS = 256;
 constexpr int KUF_PER_THREAD = 4;
 constexpr int KUF_CHUNK = KUF_THREADS * KUF_PER_THREAD;
-
-struct KufGrid {
-  int d;
-  int64_t m[3];
-  const void* g[3];
-};
-
-// s: SqExp / Gneiting -> sum ((x - y) / ell)^2 ; Matern -> sum (x - y)^2   (as the reference)
-__host__ __device__ inline bool scaled_dist(int kind) { return kind == HGP_KERN_SQEXP || kind == HGP_KERN_GNEITING; }
-
-template <typename T>
-__device__ __forceinline__ T kern_eval(int kind, T s, T sig2, T ell, T kp = (T)1) {
-  if (kind == HGP_KERN_SQEXP) return sig2 * exp(-s / (T)2);
-  const T r = sqrt(s);
-  if (kind == HGP_KERN_MATERN12) return sig2 * exp(-r / ell);
-  if (kind == HGP_KERN_MATERN32) {
-    const T dp = (T)1.7320508075688772935 * r / ell;
-    return sig2 * (((T)1 + dp) * exp(-dp));
-  }
-  if (kind == HGP_KERN_GNEITING) {   // kernels.py:108-117: r = t, kp = alpha, zero beyond t = 1
-    const T pit = (T)3.14159265358979323846 * r;
-    T c = ((T)1 - r) * cos(pit) + ((T)1 / (T)3.14159265358979323846) * sin(pit);
-    c = pow((T)1 + pow(r, kp), (T)-3) * c;
-    return r > (T)1 ? (T)0 * sig2 : sig2 * c;
-  }
-  const T dp = (T)2.2360679774997896964 * r / ell;       // Matern 5/2
-  return sig2 * (((T)1 + dp + ((T)5 / (T)3) * s / (ell * ell)) * exp(-dp));
-}
 
 template <typename T>
 __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
@@ -95,8 +67,6 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid(KufGrid g, const T* __
 // The reference builds the (M, nobs*npts, D) broadcast; here a block owns (n, outer index o):
 // the sample points alpha_a x_n and their outer-axis squared distances are block constants in
 // LDS, threads stride the last axis and sum the npts kernel values in registers.
-constexpr int SEMI_MAX_NPTS = 1024;
-
 template <typename T>
 __global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_mc(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
                                                             T sig2, T ell, T kp, int npts,

@@ -1,0 +1,396 @@
+// hgp_kuf_mv.hip — products with the grid cross covariances without storing them:
+//   out[n, s] = sum_j Kuf[n, j] w[s, j],   Kuf (nobs, M) as hgp_kuf.hip writes it, w (nw, M) rows.
+// With w = K^-1 R qm this is the posterior mean at nobs points from ONE solve (the reference
+// solves once per point: hipgp.py:416-446 through svi_gp.py:72 and hipgp.py:117-146); with
+// several weight rows, joint draws of the projected process.  The element values come from the
+// same device functions as the forwards (hgp_kuf_eval.hpp).
+//
+// Point observations (k_kuf_grid_mv), the hot path: compute bound, nobs * M kernel values each
+// used nw times.  A block is ONE wave and owns a tile of 64 points, one per lane: the lane's
+// coordinates and up to 8 accumulators sit in registers.  The block sweeps a slice of the grid
+// in mesh order; everything indexed by the grid point (its coordinates, the w values) is the
+// same for all lanes, so those loads are wave-uniform (scalar loads, no LDS), and the outer
+// axes' squared distances are hoisted out of the last-axis loop.  One kernel evaluation feeds
+// NW fused multiply-adds.  nw > 8 runs in groups of weight rows (8, 4 or 1 wide; a group's
+// unused slots repeat its last row and are not written).
+//
+// Summation: products are added in the tensor dtype over runs of at most MV_RUN consecutive
+// points of the last axis, the runs in fp64 in mesh order.  Few points: the grid is cut into
+// nsplit slices of whole MV_UNIT-point units, partial sums part[slice][n][slot] (fp64) are
+// added in slice order by k_kuf_mv_finish.  No atomics: equal arguments give equal bits.
+//
+// Line-integral observations (k_kuf_semi_mv) keep the forwards' structure: a block owns one
+// observation and a range of outer indices, threads stride the last axis, the per-thread fp64
+// sums go through a fixed-order block reduction.  Slices are ranges of outer indices.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hgp_kuf_eval.hpp"
+
+namespace hgp {
+
+constexpr int MV_TILE = 64;       // points per block of the point kernel (one wave)
+constexpr int MV_UNIT = 64;       // grid points per unit of the split
+constexpr int MV_RUN = 256;       // longest run summed in the tensor dtype
+constexpr int MV_THREADS = 256;   // block of the line-integral kernels
+constexpr int MV_MIN_UNITS = 4;   // nsplit = 0 leaves a slice at least this many units
+
+template <typename T, int KIND, int NW>
+__global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2, T ell,
+                                                        const T* __restrict__ w, int nwv, int64_t M, int nsplit,
+                                                        int64_t nunit, double* __restrict__ part,
+                                                        T* __restrict__ out, int64_t ldo) {
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  const int64_t slice = (int64_t)blockIdx.x % nsplit;
+  const int64_t tile = (int64_t)blockIdx.x / nsplit;
+  const int64_t nl = tile * MV_TILE + threadIdx.x;
+  const bool live = nl < B;
+  const int64_t n = live ? nl : B - 1;                      // a tail lane repeats the last point
+  const int64_t j0 = (slice * nunit / nsplit) * MV_UNIT;
+  int64_t j1 = ((slice + 1) * nunit / nsplit) * MV_UNIT;
+  if (j1 > M) j1 = M;
+  constexpr bool sq = KIND == HGP_KERN_SQEXP || KIND == HGP_KERN_GNEITING;
+  T xv[3] = {0, 0, 0};
+  for (int a = 0; a < d; ++a) xv[a] = x[n * d + a];
+  const T xl = xv[d - 1];
+  const T* g0 = reinterpret_cast<const T*>(g.g[0]);
+  const T* g1 = reinterpret_cast<const T*>(g.g[d > 1 ? 1 : 0]);
+  const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
+  const T* wp[NW];
+#pragma unroll
+  for (int s = 0; s < NW; ++s) wp[s] = w + (int64_t)(s < nwv ? s : nwv - 1) * M;
+  double acc[NW];
+#pragma unroll
+  for (int s = 0; s < NW; ++s) acc[s] = 0;
+  for (int64_t o = j0 / inner; o * inner < j1; ++o) {
+    const int64_t base = o * inner;
+    const int64_t ia = j0 > base ? j0 - base : 0;
+    const int64_t ib = j1 - base < inner ? j1 - base : inner;
+    // outer axes: summed in axis order, as k_kuf_grid
+    T so = 0;
+    if (d == 2) {
+      T dv = xv[0] - g0[o];
+      if (sq) dv = dv / ell;
+      so = dv * dv;
+    } else if (d == 3) {
+      T dv = xv[0] - g0[o / g.m[1]];
+      if (sq) dv = dv / ell;
+      T dw = xv[1] - g1[o % g.m[1]];
+      if (sq) dw = dw / ell;
+      so = dv * dv + dw * dw;
+    }
+    for (int64_t i0 = ia; i0 < ib; i0 += MV_RUN) {
+      const int64_t i1 = i0 + MV_RUN < ib ? i0 + MV_RUN : ib;
+      T run[NW];
+#pragma unroll
+      for (int s = 0; s < NW; ++s) run[s] = 0;
+#pragma unroll 4
+      for (int64_t i = i0; i < i1; ++i) {
+        T dv = xl - gl[i];
+        if (sq) dv = dv / ell;
+        const T sv = so + dv * dv;                           // d = 1: so = 0, the same bits as dv * dv
+        const T kv = kern_eval<T>(KIND, sv, sig2, ell);
+#pragma unroll
+        for (int s = 0; s < NW; ++s) run[s] += kv * wp[s][base + i];
+      }
+#pragma unroll
+      for (int s = 0; s < NW; ++s) acc[s] += (double)run[s];
+    }
+  }
+  if (!live) return;
+  if (part != nullptr) {
+    double* p = part + (slice * B + n) * NW;
+#pragma unroll
+    for (int s = 0; s < NW; ++s) p[s] = acc[s];
+  } else {
+#pragma unroll
+    for (int s = 0; s < NW; ++s)
+      if (s < nwv) out[n * ldo + s] = (T)acc[s];
+  }
+}
+
+// out[n, s] = sum over the slices, in slice order, of part[slice][n][s]  (s < nwv of NW slots)
+template <typename T>
+__global__ __launch_bounds__(256) void k_kuf_mv_finish(const double* __restrict__ part, int nsplit, int64_t B, int NW,
+                                                      int nwv, T* __restrict__ out, int64_t ldo) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= B * NW) return;
+  const int64_t n = t / NW;
+  const int s = (int)(t % NW);
+  if (s >= nwv) return;
+  double a = 0;
+  for (int k = 0; k < nsplit; ++k) a += part[((int64_t)k * B + n) * NW + s];
+  out[n * ldo + s] = (T)a;
+}
+
+// the NW sums of a block in a fixed order: lanes by the xor butterfly, waves in wave order
+template <int NW>
+__device__ __forceinline__ void mv_block_sum(double (&a)[NW], double* __restrict__ dst, int nwv) {
+  __shared__ double red[MV_THREADS / 64][NW];
+#pragma unroll
+  for (int s = 0; s < NW; ++s)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a[s] += __shfl_xor(a[s], off, 64);
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int s = 0; s < NW; ++s) red[wv][s] = a[s];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nwv) {
+    double t = 0;
+    for (int k = 0; k < MV_THREADS / 64; ++k) t += red[k][threadIdx.x];
+    dst[threadIdx.x] = t;
+  }
+}
+
+// MODE 1: the Monte-Carlo line integral of k_kuf_semi_mc; MODE 2: the analytic SqExp one of
+// k_kuf_semi_sqexp.  Block (n, slice of outer indices); element values formed as the forwards do.
+template <typename T, int MODE, int NW>
+__global__ __launch_bounds__(MV_THREADS) void k_kuf_semi_mv(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
+                                                           T sig2, T ell, T kp, int npts, const T* __restrict__ u,
+                                                           const T* __restrict__ w, int nwv, int64_t M, int nsplit,
+                                                           double* __restrict__ part, T* __restrict__ out,
+                                                           int64_t ldo) {
+  __shared__ T so_s[MODE == 1 ? SEMI_MAX_NPTS : 1];
+  __shared__ T xl_s[MODE == 1 ? SEMI_MAX_NPTS : 1];
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  int64_t outer = 1;
+  for (int a = 0; a < d - 1; ++a) outer *= g.m[a];
+  const int64_t slice = (int64_t)blockIdx.x % nsplit;
+  const int64_t n = (int64_t)blockIdx.x / nsplit;           // < B: the grid is B * nsplit blocks
+  const int64_t o0 = slice * outer / nsplit, o1 = (slice + 1) * outer / nsplit;
+  const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
+  const T* wp[NW];
+#pragma unroll
+  for (int s = 0; s < NW; ++s) wp[s] = w + (int64_t)(s < nwv ? s : nwv - 1) * M;
+  double acc[NW];
+#pragma unroll
+  for (int s = 0; s < NW; ++s) acc[s] = 0;
+  T xn2 = 0;
+  for (int ax = 0; ax < d; ++ax) xn2 += x[n * d + ax] * x[n * d + ax];
+  const T dist = sqrt(xn2);
+
+  if (MODE == 1) {
+    const bool sq = scaled_dist(kind);
+    const T uoff = u[0] * (T)(1.0 / (double)npts);
+    for (int64_t o = o0; o < o1; ++o) {                       // the same trip count for every thread
+      __syncthreads();                                        // the last row's readers are done
+      for (int a = threadIdx.x; a < npts; a += MV_THREADS) {
+        const T al = (T)a / (T)npts + uoff;
+        auto sqd = [&](int ax, int64_t ia) -> T {
+          T dv = reinterpret_cast<const T*>(g.g[ax])[ia] - x[n * d + ax] * al;
+          if (sq) dv = dv / ell;
+          return dv * dv;
+        };
+        T so = 0;
+        if (d == 2) so = sqd(0, o);
+        if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
+        so_s[a] = so;
+        xl_s[a] = x[n * d + d - 1] * al;
+      }
+      __syncthreads();
+      for (int64_t i = threadIdx.x; i < inner; i += MV_THREADS) {
+        const T ui = gl[i];
+        T ka = 0;
+        for (int a = 0; a < npts; ++a) {
+          T dv = ui - xl_s[a];
+          if (sq) dv = dv / ell;
+          const T sv = (d == 1) ? dv * dv : so_s[a] + dv * dv;
+          ka += kern_eval<T>(kind, sv, sig2, ell, kp);
+        }
+        const T kv = ka / (T)npts * dist;
+#pragma unroll
+        for (int s = 0; s < NW; ++s) acc[s] += (double)(kv * wp[s][o * inner + i]);
+      }
+    }
+  } else {
+    const T sinv = (T)1 / (ell * ell);
+    const T sqrt2 = (T)1.4142135623730950488, sqrt2pi = (T)2.5066282746310005024;
+    T xs[3];
+    T av = 0;
+    for (int ax = 0; ax < d; ++ax) {
+      const T xv = x[n * d + ax];
+      xs[ax] = xv * sinv;
+      av += xs[ax] * xv;
+    }
+    const T scale = sqrt((T)1 / av);
+    for (int64_t o = o0; o < o1; ++o) {
+      int64_t oi[2] = {0, 0};
+      if (d == 2) oi[0] = o;
+      if (d == 3) { oi[0] = o / g.m[1]; oi[1] = o % g.m[1]; }
+      T bo = 0, co = 0;
+      for (int ax = 0; ax < d - 1; ++ax) {
+        const T ua = reinterpret_cast<const T*>(g.g[ax])[oi[ax]];
+        bo += xs[ax] * ua;
+        co += (ua * sinv) * ua;
+      }
+      for (int64_t i = threadIdx.x; i < inner; i += MV_THREADS) {
+        const T ui = gl[i];
+        const T b = (d == 1) ? xs[0] * ui : bo + xs[d - 1] * ui;
+        const T c = (d == 1) ? (ui * sinv) * ui : co + (ui * sinv) * ui;
+        const T loc = b / av;
+        const T coef = sig2 * exp((b * b) / ((T)2 * av) - c / (T)2) * sqrt2pi * scale;
+        const T ca = (T)0.5 * ((T)1 + erf(((T)1 - loc) / (scale * sqrt2)));
+        const T cb = (T)0.5 * ((T)1 + erf(((T)0 - loc) / (scale * sqrt2)));
+        const T kv = coef * (ca - cb) * dist;
+#pragma unroll
+        for (int s = 0; s < NW; ++s) acc[s] += (double)(kv * wp[s][o * inner + i]);
+      }
+    }
+  }
+  if (part != nullptr) {
+    mv_block_sum<NW>(acc, part + (slice * B + n) * NW, NW);
+  } else {
+    __shared__ double row[NW];
+    mv_block_sum<NW>(acc, row, nwv);
+    __syncthreads();
+    if ((int)threadIdx.x < nwv) out[n * ldo + threadIdx.x] = (T)row[threadIdx.x];
+  }
+}
+
+static int mv_cus(hipError_t* e) {
+  static int cus[64] = {0};
+  int dev = 0;
+  *e = hipGetDevice(&dev);
+  if (*e != hipSuccess) return 0;
+  if (dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int v = 0;
+    *e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
+    if (*e != hipSuccess) return 0;
+    cus[dev] = v > 0 ? v : 256;
+  }
+  return cus[dev];
+}
+
+// the width of the next group of weight rows
+static inline int mv_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
+
+template <typename T, int KIND>
+static void launch_grid_mv(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2, T ell,
+                           const T* w, int nwv, int64_t M, int nsplit, int64_t nunit, double* part, T* out,
+                           int64_t ldo) {
+  if (NW == 8)
+    hipLaunchKernelGGL((k_kuf_grid_mv<T, KIND, 8>), dim3(nb), dim3(MV_TILE), 0, s, g, x, B, sig2, ell, w, nwv, M,
+                       nsplit, nunit, part, out, ldo);
+  else if (NW == 4)
+    hipLaunchKernelGGL((k_kuf_grid_mv<T, KIND, 4>), dim3(nb), dim3(MV_TILE), 0, s, g, x, B, sig2, ell, w, nwv, M,
+                       nsplit, nunit, part, out, ldo);
+  else
+    hipLaunchKernelGGL((k_kuf_grid_mv<T, KIND, 1>), dim3(nb), dim3(MV_TILE), 0, s, g, x, B, sig2, ell, w, nwv, M,
+                       nsplit, nunit, part, out, ldo);
+}
+
+template <typename T, int MODE>
+static void launch_semi_mv(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, int kind,
+                           T sig2, T ell, T kp, int npts, const T* u, const T* w, int nwv, int64_t M, int nsplit,
+                           double* part, T* out, int64_t ldo) {
+  if (NW == 8)
+    hipLaunchKernelGGL((k_kuf_semi_mv<T, MODE, 8>), dim3(nb), dim3(MV_THREADS), 0, s, g, x, B, kind, sig2, ell, kp,
+                       npts, u, w, nwv, M, nsplit, part, out, ldo);
+  else if (NW == 4)
+    hipLaunchKernelGGL((k_kuf_semi_mv<T, MODE, 4>), dim3(nb), dim3(MV_THREADS), 0, s, g, x, B, kind, sig2, ell, kp,
+                       npts, u, w, nwv, M, nsplit, part, out, ldo);
+  else
+    hipLaunchKernelGGL((k_kuf_semi_mv<T, MODE, 1>), dim3(nb), dim3(MV_THREADS), 0, s, g, x, B, kind, sig2, ell, kp,
+                       npts, u, w, nwv, M, nsplit, part, out, ldo);
+}
+
+// mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs > 0, nw > 0, nsplit >= 0.
+template <typename T>
+static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
+                               const void* xv, int64_t nobs, double sig2, double ell, int npts, const void* uv,
+                               const void* wv, int64_t nw, int64_t nsplit_in, void* outv, hipStream_t s) {
+  KufGrid g{};
+  g.d = ndim;
+  int64_t outer = 1, M = 1;
+  for (int a = 0; a < ndim; ++a) {
+    g.m[a] = m[a];
+    g.g[a] = grids[a];
+    M *= m[a];
+    if (a < ndim - 1) outer *= m[a];
+  }
+  const T* x = reinterpret_cast<const T*>(xv);
+  const T* w = reinterpret_cast<const T*>(wv);
+  const T* u = reinterpret_cast<const T*>(uv);
+  T* out = reinterpret_cast<T*>(outv);
+  // the split: a pure function of (nobs, M, nw) and the CU count unless the caller forces it
+  const int64_t nunit = mode == 0 ? (M + MV_UNIT - 1) / MV_UNIT : outer;
+  const int64_t nrow = mode == 0 ? (nobs + MV_TILE - 1) / MV_TILE : nobs;      // blocks per slice
+  int64_t nsplit = nsplit_in;
+  if (nsplit == 0) {
+    hipError_t e = hipSuccess;
+    const int64_t target = (int64_t)(mode == 0 ? 16 : 4) * mv_cus(&e);          // blocks that fill the device
+    if (e != hipSuccess) return e;
+    const int64_t most = mode == 0 ? nunit / MV_MIN_UNITS : nunit;
+    nsplit = (target + nrow - 1) / nrow;
+    if (nsplit > most) nsplit = most;
+    if (nsplit < 1) nsplit = 1;
+  }
+  if (nsplit > nunit) nsplit = nunit;
+  if (nrow * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+  const unsigned nb = (unsigned)(nrow * nsplit);
+  double* part = nullptr;
+  if (nsplit > 1) {
+    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part),
+                                  (size_t)nsplit * (size_t)nobs * (size_t)mv_group(nw) * sizeof(double), s);
+    if (e != hipSuccess) return e;
+  }
+  for (int64_t s0 = 0; s0 < nw;) {
+    const int NW = mv_group(nw - s0);
+    const int nwv = (int)(nw - s0 < NW ? nw - s0 : NW);
+    const T* wg = w + s0 * M;
+    T* og = out + s0;
+    if (mode == 0) {
+      switch (kind) {
+        case HGP_KERN_SQEXP:
+          launch_grid_mv<T, HGP_KERN_SQEXP>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
+                                            part, og, nw);
+          break;
+        case HGP_KERN_MATERN12:
+          launch_grid_mv<T, HGP_KERN_MATERN12>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
+                                               part, og, nw);
+          break;
+        case HGP_KERN_MATERN32:
+          launch_grid_mv<T, HGP_KERN_MATERN32>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
+                                               part, og, nw);
+          break;
+        default:
+          launch_grid_mv<T, HGP_KERN_MATERN52>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
+                                               part, og, nw);
+      }
+    } else if (mode == 1) {
+      launch_semi_mv<T, 1>(NW, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, wg, nwv, M, (int)nsplit, part,
+                           og, nw);
+    } else {
+      launch_semi_mv<T, 2>(NW, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, wg, nwv, M, (int)nsplit, part,
+                           og, nw);
+    }
+    if (part != nullptr) {
+      const int64_t tot = nobs * NW;
+      hipLaunchKernelGGL((k_kuf_mv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
+                         (int)nsplit, nobs, NW, nwv, og, nw);
+    }
+    s0 += nwv;
+  }
+  hipError_t e = hipGetLastError();
+  if (part != nullptr) {
+    const hipError_t f = hipFreeAsync(part, s);
+    if (e == hipSuccess) e = f;
+  }
+  return e;
+}
+
+// launcher behind hgp_kuf_grid_matvec / hgp_kuf_semi_mc_matvec / hgp_kuf_semi_sqexp_matvec
+hipError_t kuf_matvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
+                      const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* w,
+                      int64_t nw, int64_t nsplit, void* out, hipStream_t s) {
+  if (dtype == HGP_F32)
+    return kuf_matvec_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out, s);
+  return kuf_matvec_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out, s);
+}
+
+}  // namespace hgp

@@ -11,6 +11,10 @@ Kernel-hyper-parameter learning has fused twins, `kuf_grid_ad` / `kuf_semi_mc_ad
 `kuf_semi_sqexp_ad`: the same forward, and the gradient with respect to (sig2, ell) by
 hgp_kuf_*_grad, which recomputes K instead of keeping the broadcast for autograd
 (`SviGP._make_grams` uses them when the model's `kuf_grad` knob is on).
+
+Products with Knm that never store it, `kuf_grid_matvec` / `kuf_semi_mc_matvec` /
+`kuf_semi_sqexp_matvec` (hgp_kuf_*_matvec): Knm @ W^T for a few weight rows W, what the posterior
+mean and draws at many points need once K^-1 R v is solved (`ToeplitzInducingGP.predict_mean`).
 """
 import ctypes
 
@@ -126,6 +130,83 @@ def kuf_semi_sqexp(kernel, xgrids, x, params):
     m, ptrs = _grid_ptrs(grids)
     check(lib().hgp_kuf_semi_sqexp(_lib.dtype_code(x.dtype), len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
                                    x.shape[0], s2, el, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+# ---- products with the cross covariances, Knm never stored (hgp_kuf_*_matvec) -------------------
+
+def _matvec_weights(W, x, M):
+    """W as contiguous (nw, M) rows on x's device in x's dtype, or None where the product declines
+    (W carries a graph that the kernel would drop)."""
+    if torch.is_grad_enabled() and W.requires_grad:
+        return None
+    W = W.detach()
+    if W.dim() == 1:
+        W = W[None, :]
+    if W.dim() != 2 or W.shape[1] != M:
+        raise ValueError(f"W must be (nw, M) or (M,) with M = {M}, got {tuple(W.shape)}")
+    return W.to(device=x.device, dtype=x.dtype).contiguous()
+
+
+def kuf_grid_matvec(kernel, xgrids, x, params, W, nsplit=0):
+    """kuf_grid(...) @ W^T as an (nobs, nw) tensor without the (nobs, M) matrix
+    (hgp_kuf_grid_matvec): W is (nw, M) or (M,).  nsplit: slices of the grid summed apart (0: the
+    library's choice).  None under the rules by which `kuf_grid` declines."""
+    a = _grid_call_args(kernel, xgrids, x, params)
+    if a is None:
+        return None
+    kind, s2, el, grids, xc, M = a
+    Wc = _matvec_weights(W, x, M)
+    if Wc is None:
+        return None
+    out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(grids)
+    check(lib().hgp_kuf_grid_matvec(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
+                                    x.shape[0], s2, el, ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
+                                    ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_semi_mc_matvec(kernel, xgrids, x, params, npts, u=None, W=None, nsplit=0):
+    """kuf_semi_mc(...) @ W^T as an (nobs, nw) tensor without the (nobs, M) matrix
+    (hgp_kuf_semi_mc_matvec); the offset draw `u` as in `kuf_semi_mc`."""
+    a = _grid_call_args(kernel, xgrids, x, params, gneiting=True)
+    if a is None:
+        return None
+    kind, s2, el, grids, xc, M = a
+    if W is None:
+        raise TypeError("kuf_semi_mc_matvec needs the weight rows W")
+    Wc = _matvec_weights(W, x, M)
+    if Wc is None:
+        return None
+    if u is None:
+        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
+    u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
+    out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(grids)
+    kp = float(getattr(kernel, "alpha", 1.))
+    check(lib().hgp_kuf_semi_mc_matvec(_lib.dtype_code(x.dtype), kind, kp, len(grids), m, ptrs,
+                                       ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el, int(npts),
+                                       ctypes.c_void_p(u.data_ptr()), ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0],
+                                       int(nsplit), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_semi_sqexp_matvec(kernel, xgrids, x, params, W, nsplit=0):
+    """kuf_semi_sqexp(...) @ W^T as an (nobs, nw) tensor without the (nobs, M) matrix
+    (hgp_kuf_semi_sqexp_matvec); SqExp only, like the forward."""
+    a = _grid_call_args(kernel, xgrids, x, params)
+    if a is None or a[0] != _lib.KERN_SQEXP:
+        return None
+    kind, s2, el, grids, xc, M = a
+    Wc = _matvec_weights(W, x, M)
+    if Wc is None:
+        return None
+    out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(grids)
+    check(lib().hgp_kuf_semi_sqexp_matvec(_lib.dtype_code(x.dtype), len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
+                                          x.shape[0], s2, el, ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
+                                          ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
     return out
 
 

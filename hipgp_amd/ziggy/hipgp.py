@@ -390,6 +390,118 @@ class ToeplitzInducingGP(SviGP):
         sig = torch.sqrt(ktilde + self.compute_knSkn(kn, qS))[:, None]
         return mu.cpu().detach(), sig.cpu().detach()
 
+    # ---- the posterior mean and draws at any number of points from ONE solve -------------------
+    # kn(x).v = Knm(x) K^-1 R v = sum_j k(x, u_j) alpha_j with alpha = K^-1 R v an M-vector that
+    # does not depend on x: one single-RHS solve, then a product with Knm that never stores it
+    # (hgp_kuf_*_matvec).  `predict` solves once per point (`hipgp.py:416-446`); it stays as it is
+    # and still owns the predictive sd, which needs those solves.
+    _NO_MEAN_WEIGHTS = ("mean_weights / predict_mean / predict_draws need whitened_type='ziggy': they solve "
+                        "K alpha = R v with the Toeplitz operators, and cholesky whitening has no circulant R")
+
+    def variational_draws(self, n, eps=None, generator=None):
+        """(n, M') rows v_s = qm + S^{1/2} eps_s of the whitened variational posterior on the device;
+        eps (n, M') standard normal draws (given, for reproducibility, or from torch.randn with
+        `generator`).  The family supplies S^{1/2}."""
+        raise NotImplementedError
+
+    def _draw_eps(self, n, eps, generator):
+        dev = self.xgrids[0].device
+        if eps is None:
+            return torch.randn((int(n), self.Mprime), generator=generator, dtype=self.dtype, device=dev)
+        if tuple(eps.shape) != (int(n), self.Mprime):
+            raise ValueError(f"eps must be (n, M') = ({int(n)}, {self.Mprime}), got {tuple(eps.shape)}")
+        return eps.detach().to(device=dev, dtype=self.dtype, copy=True)         # the caller's eps stays
+
+    def mean_weights(self, v=None, maxiter_cg=50, tol=1e-8, Kmm=None):
+        """alpha = K^-1 R v as (nv, M) rows on the device, no graph: one `_matmul_by_R` and one
+        preconditioned solve of nv right-hand sides (in place where `inv_matmul_` allows).  v: (nv, M')
+        rows, an M'-vector or an (M', 1) column in the whitened space; None means qm.  The rows
+        depend on the model state only, so a caller may keep them across `predict_mean` calls."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        with torch.no_grad():
+            if Kmm is None:
+                Kmm = self.toeplitz()
+            if v is None:
+                v = self.standard_variational_params()[0]
+            v = v.detach()
+            if v.dim() == 1 or tuple(v.shape) == (self.Mprime, 1):
+                v = v.reshape(1, -1)
+            if v.dim() != 2 or v.shape[1] != self.Mprime:
+                raise ValueError(f"v must be (nv, M') rows with M' = {self.Mprime}, got {tuple(v.shape)}")
+            nv = v.shape[0]
+            rows = v.to(device=self.xgrids[0].device, dtype=self.dtype).contiguous()
+            if hasattr(Kmm, "set_batch_shape"):
+                Kmm.set_batch_shape((nv,))
+            b = Kmm._matmul_by_R(rows).reshape(nv, self.M)
+            if hasattr(Kmm, "inv_matmul_") and b.is_contiguous() and not Kmm.column.requires_grad:
+                return Kmm.inv_matmul_(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
+            return Kmm.inv_matmul(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
+
+    def _kuf_product(self, x, W, integrated_obs, estimator, samps, mc_offset, batch_size):
+        """Knm(x) W^T, (N, nw) on the device, for weight rows W (nw, M): the fused products of
+        `hipgp_amd.kuf` where they apply (Knm never stored), else `_make_grams(piece)[0] @ W^T` over
+        pieces of `batch_size` points (None: a piece whose Knm stays under 256 MiB) -- every kernel,
+        the "numerical" estimator and CPU stand-ins take that route."""
+        from hipgp_amd import kuf
+        params = self.get_kernel_params()
+        out = None
+        if not integrated_obs:
+            out = kuf.kuf_grid_matvec(self.kernel, self.xgrids, x, params, W)
+        elif estimator == "analytic":
+            out = kuf.kuf_semi_sqexp_matvec(self.kernel, self.xgrids, x, params, W)
+        elif estimator == "mc-biased":
+            out = kuf.kuf_semi_mc_matvec(self.kernel, self.xgrids, x, params, samps, u=mc_offset, W=W)
+        if out is not None:
+            return out
+        if batch_size is None:
+            batch_size = max(1, (256 << 20) // (self.M * x.element_size()))
+        pieces = [self._make_grams(x[a:a + batch_size], integrated_obs=integrated_obs,
+                                   semi_integrated_estimator=estimator, semi_integrated_samps=samps,
+                                   mc_offset=mc_offset)[0].matmul(W.t())
+                  for a in range(0, x.shape[0], int(batch_size))]
+        return torch.cat(pieces, dim=0) if pieces else W.new_zeros((0, W.shape[0]))
+
+    def predict_mean(self, x, integrated_obs=False, semi_integrated_estimator="analytic",
+                     semi_integrated_samps=10, maxiter_cg=50, Kmm=None, weights=None, batch_size=None,
+                     mc_offset=None):
+        """E[f(x)] alone, on the CPU and shaped like `predict`'s mu, from one single-RHS solve
+        however many points x holds: kn(x).qm = Knm(x) alpha, alpha = `mean_weights()` (or the
+        caller's `weights`, kept from an earlier call), the product by `_kuf_product`.  The sd is
+        not available this way (it needs kn itself): use `predict`.  With the "mc-biased" estimator
+        and no `mc_offset` the fused product draws one offset for all of x, the fallback one per
+        piece, as `_make_grams` would."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        with torch.no_grad():
+            x = x.to(self.xgrids[0].device)
+            if weights is None:
+                weights = self.mean_weights(maxiter_cg=maxiter_cg, Kmm=Kmm)
+            mu = self._kuf_product(x, weights.reshape(-1, self.M)[:1], integrated_obs, semi_integrated_estimator,
+                                   semi_integrated_samps, mc_offset, batch_size)
+            return mu.reshape(-1, 1).cpu().detach()
+
+    def predict_draws(self, x, n, eps=None, generator=None, integrated_obs=False,
+                      semi_integrated_estimator="analytic", semi_integrated_samps=10, maxiter_cg=50, Kmm=None,
+                      batch_size=None, mc_offset=None):
+        """n joint draws at the points x, (n, N) on the CPU: kn(x).v_s for v_s = qm + S^{1/2} eps_s
+        (`variational_draws`; eps (n, M') makes them reproducible), from one solve of n right-hand
+        sides and one fused product with n weight rows.
+
+        These are draws of the PROJECTED process K_xu K^-1 u with u = R v the inducing values: their
+        mean is `predict`'s mean and their variance is the kn S kn term of its variance.  They
+        exclude the residual `ktilde` = Knn - |kn|^2 that `predict`'s sd adds, so between inducing
+        points they are smoother and narrower than draws of f itself."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        with torch.no_grad():
+            x = x.to(self.xgrids[0].device)
+            v = self.variational_draws(n, eps=eps, generator=generator)
+            alpha = self.mean_weights(v, maxiter_cg=maxiter_cg, Kmm=Kmm)
+            out = self._kuf_product(x, alpha, integrated_obs, semi_integrated_estimator, semi_integrated_samps,
+                                    mc_offset, batch_size)
+            return out.t().contiguous().cpu().detach()
+
 
 class MeanFieldToeplitzGP(ToeplitzInducingGP):
     """Diagonal variational covariance in the expanded space (`hipgp.py:449-524`)."""
@@ -522,6 +634,14 @@ class MeanFieldToeplitzGP(ToeplitzInducingGP):
                 row = lambda t: t.detach().reshape(1, -1).to(device=dev, dtype=self.dtype)
                 v.mul_(torch.sqrt(row(qS))).add_(row(qm))
             return Kmm._matmul_by_R(self._grid_rows(Kmm, v, int(n))).reshape(int(n), *dims)
+
+    def variational_draws(self, n, eps=None, generator=None):
+        """v_s = qm + sqrt(qS) * eps_s, (n, M') on the device (the rows `sample_grid` applies R to)."""
+        with torch.no_grad():
+            v = self._draw_eps(n, eps, generator)
+            qm, qS = self.standard_variational_params()
+            row = lambda t: t.detach().reshape(1, -1).to(device=v.device, dtype=self.dtype)
+            return v.mul_(torch.sqrt(row(qS))).add_(row(qm))
 
     def fit_stats(self, Knm, ybatch, Knn_diag, noise_std_batch=None, maxiter_cg=10, Kmm=None):
         """`batch_stats` of kn = R^T K^-1 Knm^T (`hipgp.py:234-250`) without the (bsz, M') kn:
@@ -826,6 +946,15 @@ class BlockToeplitzGP(ToeplitzInducingGP):
         if qm is None or qS is None:
             qm, qS = self.standard_variational_params()
         return block_kl_to_standard(qm, qS)
+
+    def variational_draws(self, n, eps=None, generator=None):
+        """v_s = qm + L eps_s with L the per-block Cholesky factor of S (L L^T = S), (n, M') on the
+        device in grid order."""
+        with torch.no_grad():
+            v = self._draw_eps(n, eps, generator)
+            qm, qS = self.standard_variational_params()
+            L = torch.linalg.cholesky(qS.detach().to(device=v.device, dtype=self.dtype))
+            return self.block_diag_multiply(L, v) + qm.detach().reshape(1, -1).to(device=v.device, dtype=self.dtype)
 
     # ---- the streamed route: the batch sums without the (bsz, M') kn ---------------------------
     # right-hand sides per piece of kn held at a time (hgp_rt_block_stats' piece_rhs); 0: its default

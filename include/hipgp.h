@@ -295,6 +295,50 @@ int hgp_kuf_semi_sqexp_grad(int dtype, int ndim, const int64_t* m, const void* c
                             const void* x, int64_t nobs, double sig2, double ell,
                             const void* g, void* grad2, void* hip_stream);
 
+/* Product with the point-observation cross covariance, never stored:
+ *   out[n, s] = sum_j Kuf[n, j] w[s, j],   Kuf[n, j] = k(x_n, u_j) exactly as hgp_kuf_grid writes it,
+ *   w: (nw, M) rows, out: (nobs, nw) rows, both device arrays of dtype; x, grids, kind as hgp_kuf_grid
+ *   (HGP_KERN_GNEITING refused as there).
+ * With w = K^-1 R qm the posterior mean E[f(x_n)] = kn(x_n).qm at any number of points from one
+ * single-RHS solve: replaces, for the mean, the per-point route of hipgp.py:416-446 (Knm row by
+ * svi_gp.py:72, its solve and R^T by hipgp.py:117-146, the dot with qm at hipgp.py:436).  With
+ * several rows w_s = K^-1 R v_s, joint draws kn(x).v_s at arbitrary points (the reference leaves
+ * sample() a TODO, hipgp.py:111-115).
+ * A block owns 64 points and sweeps a slice of the grid; products are summed in dtype over runs of
+ * at most 256 points of the last axis, the runs in fp64.  nsplit: slices the grid is cut into
+ * (whole units of 64 mesh points), their fp64 partial sums added in slice order by a second kernel.
+ * 0: chosen from (nobs, M) and the device's CU count alone (about 16 blocks per CU, a slice at
+ * least 256 mesh points); > 0: that many, at most ceil(M / 64).  No atomics: the same bits on
+ * every call with the same arguments on the same device.
+ * Scratch, nsplit > 1 only: nsplit * nobs * min(nw, 8) fp64, stream-ordered (hipMallocAsync /
+ * hipFreeAsync on hip_stream); with nsplit = 0 at most (16 CUs + nobs / 64) * 4 KiB, under
+ * 32 MiB at 256 CUs (from 16 CUs tiles of 64 points on, the grid is one slice: no scratch).
+ * nobs = 0 or nw = 0: nothing written, 0 returned.  HGP_E_ARG (before any HIP call): null pointer,
+ * bad dtype / kind / ndim, a grid size < 1, nobs / nw / nsplit < 0.  HGP_E_HIP: the launch or the
+ * scratch allocation failed (more than 2^31 - 1 blocks: nobs / 64 * nsplit). */
+int hgp_kuf_grid_matvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                        const void* x, int64_t nobs, double sig2, double ell,
+                        const void* w, int64_t nw, int64_t nsplit, void* out, void* hip_stream);
+
+/* The same product with the Monte-Carlo line-integral cross covariance of hgp_kuf_semi_mc
+ * (Kernel.k_semi_mc, kernels.py:19-39, as svi_gp.py:61-64 uses it): element values, kind (any
+ * HGP_KERN_*), kparam, npts (1..1024, else HGP_E_ARG) and the offset draw u as there.  A block owns
+ * one observation and a range of outer mesh indices (all axes but the last); per-thread fp64 sums,
+ * a fixed-order block reduction.  nsplit counts ranges of outer indices: 0 picks about 4 blocks per
+ * CU, > 0 is clamped to the number of outer indices (1 for a 1-D grid).  Scratch and errors as
+ * hgp_kuf_grid_matvec (nsplit * nobs * min(nw, 8) fp64 when nsplit > 1). */
+int hgp_kuf_semi_mc_matvec(int dtype, int kind, double kparam, int ndim, const int64_t* m,
+                           const void* const* grids, const void* x, int64_t nobs, double sig2,
+                           double ell, int npts, const void* u, const void* w, int64_t nw,
+                           int64_t nsplit, void* out, void* hip_stream);
+
+/* The same product with the analytic SqExp line integral of hgp_kuf_semi_sqexp (SqExp.k_semi ->
+ * semi_integrated_sqe, kernels.py:80-85, 223-237): SqExp only like its forward, NaN rows for
+ * |x_n| = 0 as there.  Structure, nsplit, scratch and errors as hgp_kuf_semi_mc_matvec. */
+int hgp_kuf_semi_sqexp_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids,
+                              const void* x, int64_t nobs, double sig2, double ell,
+                              const void* w, int64_t nw, int64_t nsplit, void* out, void* hip_stream);
+
 /* Doubly-integrated diagonal Knn_diag by table interpolation,
  * KernelDoublyDiagInterpolator.forward (kernels.py:200-220): table = device array of 3*N
  * values in dtype (distance grid, knn, slopes: the reference's float32 table), x: (nobs,
