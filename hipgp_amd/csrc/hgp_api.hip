@@ -2319,6 +2319,57 @@ int hgp_kuf_semi_sqexp_matvec(int dtype, int ndim, const int64_t* m, const void*
   return 0;
 }
 
+// the checks the three transposed Kuf products share; all before any HIP call.  Returns 1 when
+// there is nothing to do (nc = 0), 0 to go on (nobs = 0 included: out is zeroed), else the error.
+static int check_rmatvec_args(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                              int64_t nobs, const void* c, int64_t nc, int64_t nsplit, const void* out) {
+  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
+  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
+  if (nobs < 0 || nc < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nc and nsplit must be >= 0");
+  for (int a = 0; a < ndim; ++a)
+    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
+  if (nc == 0) return 1;
+  if (out == nullptr || (nobs > 0 && (x == nullptr || c == nullptr))) return fail(HGP_E_ARG, "null x / c / out");
+  return 0;
+}
+
+int hgp_kuf_grid_rmatvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                         int64_t nobs, double sig2, double ell, const void* c, int64_t nc, int64_t nsplit, void* out,
+                         void* hip_stream) {
+  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  hipError_t e = kuf_rmatvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, c, nc, nsplit, out,
+                             reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_rmatvec: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_mc_rmatvec(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
+                            const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u,
+                            const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream) {
+  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_GNEITING) return fail(HGP_E_ARG, "bad kernel kind");
+  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
+  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  hipError_t e = kuf_rmatvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out,
+                             reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_rmatvec: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                               int64_t nobs, double sig2, double ell, const void* c, int64_t nc, int64_t nsplit,
+                               void* out, void* hip_stream) {
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  hipError_t e = kuf_rmatvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, c, nc,
+                             nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_rmatvec: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_knn_doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* table,
                         int N, void* out, void* hip_stream) {
   if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");

@@ -96,6 +96,11 @@ hipError_t kuf_grad(int dtype, int mode, int kind, int ndim, const int64_t* m, c
 hipError_t kuf_matvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
                       const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* w,
                       int64_t nw, int64_t nsplit, void* out, hipStream_t s);
+// out = c Kuf, the transposed product, without Kuf (hgp_kuf_rmv.hip); mode as kuf_grad; nobs >= 0 (0: out zeroed),
+// nc > 0, nsplit >= 0 (0: chosen here)
+hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
+                       const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* c,
+                       int64_t nc, int64_t nsplit, void* out, hipStream_t s);
 hipError_t meanfield_stats(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* qm, const void* qS,
                            const void* y, const void* iv, const void* knn, const void* lsd, void* an, void* lam,
                            void* dm, hipStream_t s);

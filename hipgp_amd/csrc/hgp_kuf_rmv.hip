@@ -1,0 +1,401 @@
+// hgp_kuf_rmv.hip — products with the TRANSPOSED grid cross covariances without storing them:
+//   out[s, j] = sum_n Kuf[n, j] c[s, n],   Kuf (nobs, M) as hgp_kuf.hip writes it, c (nc, nobs) rows.
+// The sibling of hgp_kuf_mv.hip (out = Kuf w^T).  With both, the operator of
+//   (K + Kuf^T diag(iv) Kuf) beta = Kuf^T (iv o y)
+// runs matrix-free, which is the optimal variational mean of all observations at once
+// (`ToeplitzInducingGP.fit_mean`).  Element values come from the same device functions as the
+// forwards (hgp_kuf_eval.hpp).
+//
+// Point observations (k_kuf_grid_rmv), the hot path: compute bound, nobs * M kernel values each
+// used nc times.  The roles of k_kuf_grid_mv turned round: a block is ONE wave and owns a tile of
+// 64 mesh points, one per lane: the lane's grid coordinates and up to 8 accumulators sit in
+// registers.  The block sweeps a slice of the observations in order; everything indexed by the
+// observation (its coordinates, the nc coefficients) is the same for all lanes, so those loads
+// are wave-uniform (scalar loads, no LDS, no barrier, no vector load in the loop).  One kernel
+// evaluation feeds NC fused multiply-adds.  nc > 8 runs in groups of coefficient rows (8, 4 or 1
+// wide; a group's unused slots repeat its last row and are not written).
+//
+// Summation: products are added in the tensor dtype over runs of at most RMV_RUN consecutive
+// observations, the runs in fp64 in observation order.  Few mesh points: the observations are cut
+// into nsplit slices of whole runs, partial sums part[slice][s][j] (fp64) are added in slice
+// order by k_kuf_rmv_finish.  No atomics: equal arguments give equal bits.
+//
+// Line-integral observations (k_kuf_semi_rmv): a block is one wave and owns one outer mesh index
+// and 64 points of the last axis, one per lane; it walks its slice of the observations in order
+// and every lane adds (double)(Kuf * c) to its own fp64 sums.  For the Monte-Carlo integral the
+// sample table of (observation, outer index) is rebuilt in LDS between two barriers, as the
+// forward's product does per outer index.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hgp_kuf_eval.hpp"
+
+namespace hgp {
+
+constexpr int RMV_TILE = 64;      // mesh points per block (one wave), both kernels
+constexpr int RMV_RUN = 256;      // longest run summed in the tensor dtype; the unit of the split
+
+__device__ __forceinline__ float rmv_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double rmv_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// The squared distance of k_kuf_grid with its roundings spelled out.  There the outer axes' sum is
+// a block constant formed ahead of the last-axis term, and hipcc contracts what is left in one
+// way only: so = dv0^2 (2-D) or fma(dv0, dv0, dv1^2) (3-D), s = fma(dvl, dvl, so), s = dvl^2 (1-D).
+// Here all three products meet in one expression, where contraction could pair them differently
+// (SqExp at s = 60 turns one ulp of s into 4e-6 of the value), so it is switched off and the
+// forward's pairing is written with explicit fused multiply-adds.
+template <typename T, int D>
+__device__ __forceinline__ T rmv_sqdist(T d0, T d1, T dl) {
+#pragma clang fp contract(off)
+  if (D == 1) return dl * dl;
+  if (D == 2) return rmv_fma(dl, dl, d0 * d0);
+  return rmv_fma(dl, dl, rmv_fma(d0, d0, d1 * d1));
+}
+
+// One run [r0, r1) of observations for the lane's mesh point (u0, u1, ul): run[s] += Kuf * c.
+// D is the number of axes.
+template <typename T, int KIND, int NC, int D>
+__device__ __forceinline__ void rmv_run(const T* __restrict__ x, int64_t r0, int64_t r1, T u0, T u1, T ul, T sig2,
+                                        T ell, const T* const (&cp)[NC], T (&run)[NC]) {
+  constexpr bool sq = KIND == HGP_KERN_SQEXP || KIND == HGP_KERN_GNEITING;
+#pragma unroll 4
+  for (int64_t n = r0; n < r1; ++n) {
+    T d0 = 0, d1 = 0;
+    if (D >= 2) {
+      d0 = x[n * D] - u0;
+      if (sq) d0 = d0 / ell;
+    }
+    if (D == 3) {
+      d1 = x[n * D + 1] - u1;
+      if (sq) d1 = d1 / ell;
+    }
+    T dv = x[n * D + D - 1] - ul;
+    if (sq) dv = dv / ell;
+    const T sv = rmv_sqdist<T, D>(d0, d1, dv);
+    const T kv = kern_eval<T>(KIND, sv, sig2, ell);
+#pragma unroll
+    for (int s = 0; s < NC; ++s) run[s] += kv * cp[s][n];
+  }
+}
+
+template <typename T, int KIND, int NC>
+__global__ __launch_bounds__(RMV_TILE) void k_kuf_grid_rmv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2,
+                                                          T ell, const T* __restrict__ c, int ncv, int64_t M,
+                                                          int nsplit, int64_t nrun, double* __restrict__ part,
+                                                          T* __restrict__ out) {
+  const int d = g.d;
+  const int64_t slice = (int64_t)blockIdx.x % nsplit;
+  const int64_t tile = (int64_t)blockIdx.x / nsplit;
+  const int64_t jl = tile * RMV_TILE + threadIdx.x;
+  const bool live = jl < M;
+  const int64_t j = live ? jl : M - 1;                      // a tail lane repeats the last mesh point
+  const int64_t n0 = (slice * nrun / nsplit) * RMV_RUN;
+  int64_t n1 = ((slice + 1) * nrun / nsplit) * RMV_RUN;
+  if (n1 > B) n1 = B;
+  // the lane's mesh point: C order, last axis fastest
+  const int64_t inner = g.m[d - 1];
+  const int64_t o = j / inner;
+  const T ul = reinterpret_cast<const T*>(g.g[d - 1])[j % inner];
+  T u0 = 0, u1 = 0;
+  if (d == 2) u0 = reinterpret_cast<const T*>(g.g[0])[o];
+  if (d == 3) {
+    u0 = reinterpret_cast<const T*>(g.g[0])[o / g.m[1]];
+    u1 = reinterpret_cast<const T*>(g.g[1])[o % g.m[1]];
+  }
+  const T* cp[NC];
+#pragma unroll
+  for (int s = 0; s < NC; ++s) cp[s] = c + (int64_t)(s < ncv ? s : ncv - 1) * B;
+  double acc[NC];
+#pragma unroll
+  for (int s = 0; s < NC; ++s) acc[s] = 0;
+  for (int64_t r0 = n0; r0 < n1; r0 += RMV_RUN) {
+    const int64_t r1 = r0 + RMV_RUN < n1 ? r0 + RMV_RUN : n1;
+    T run[NC];
+#pragma unroll
+    for (int s = 0; s < NC; ++s) run[s] = 0;
+    if (d == 1)
+      rmv_run<T, KIND, NC, 1>(x, r0, r1, u0, u1, ul, sig2, ell, cp, run);
+    else if (d == 2)
+      rmv_run<T, KIND, NC, 2>(x, r0, r1, u0, u1, ul, sig2, ell, cp, run);
+    else
+      rmv_run<T, KIND, NC, 3>(x, r0, r1, u0, u1, ul, sig2, ell, cp, run);
+#pragma unroll
+    for (int s = 0; s < NC; ++s) acc[s] += (double)run[s];
+  }
+  if (!live) return;
+  if (part != nullptr) {
+    double* p = part + slice * NC * M + j;
+#pragma unroll
+    for (int s = 0; s < NC; ++s) p[(int64_t)s * M] = acc[s];
+  } else {
+#pragma unroll
+    for (int s = 0; s < NC; ++s)
+      if (s < ncv) out[(int64_t)s * M + j] = (T)acc[s];
+  }
+}
+
+// out[s, j] = sum over the slices, in slice order, of part[slice][s][j]  (s < ncv of NC slots)
+template <typename T>
+__global__ __launch_bounds__(256) void k_kuf_rmv_finish(const double* __restrict__ part, int nsplit, int64_t M, int NC,
+                                                       int ncv, T* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= M * ncv) return;                                 // t = s * M + j with s < ncv
+  const int64_t stride = (int64_t)NC * M;
+  double a = 0;
+  for (int k = 0; k < nsplit; ++k) a += part[k * stride + t];
+  out[t] = (T)a;
+}
+
+// MODE 1: the Monte-Carlo line integral of k_kuf_semi_mc; MODE 2: the analytic SqExp one of
+// k_kuf_semi_sqexp.  Block (outer index o, 64 points of the last axis, slice of the observations);
+// element values formed as the forwards do.
+template <typename T, int MODE, int NC>
+__global__ __launch_bounds__(RMV_TILE) void k_kuf_semi_rmv(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
+                                                          T sig2, T ell, T kp, int npts, const T* __restrict__ u,
+                                                          const T* __restrict__ c, int ncv, int64_t M, int nsplit,
+                                                          int64_t nrun, int64_t nchunk, double* __restrict__ part,
+                                                          T* __restrict__ out) {
+  __shared__ T so_s[MODE == 1 ? SEMI_MAX_NPTS : 1];
+  __shared__ T xl_s[MODE == 1 ? SEMI_MAX_NPTS : 1];
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  const int64_t slice = (int64_t)blockIdx.x % nsplit;
+  const int64_t tile = (int64_t)blockIdx.x / nsplit;
+  const int64_t o = tile / nchunk;                          // < outer: the grid is outer * nchunk * nsplit blocks
+  const int64_t il = (tile % nchunk) * RMV_TILE + threadIdx.x;
+  const bool live = il < inner;
+  const int64_t i = live ? il : inner - 1;                  // a tail lane repeats the row's last point
+  const int64_t n0 = (slice * nrun / nsplit) * RMV_RUN;
+  int64_t n1 = ((slice + 1) * nrun / nsplit) * RMV_RUN;
+  if (n1 > B) n1 = B;
+  const T ui = reinterpret_cast<const T*>(g.g[d - 1])[i];
+  const T* cp[NC];
+#pragma unroll
+  for (int s = 0; s < NC; ++s) cp[s] = c + (int64_t)(s < ncv ? s : ncv - 1) * B;
+  double acc[NC];
+#pragma unroll
+  for (int s = 0; s < NC; ++s) acc[s] = 0;
+
+  if (MODE == 1) {
+    const bool sq = scaled_dist(kind);
+    const T uoff = u[0] * (T)(1.0 / (double)npts);
+    for (int64_t n = n0; n < n1; ++n) {                       // the same trip count for every lane
+      __syncthreads();                                        // the last observation's readers are done
+      for (int a = threadIdx.x; a < npts; a += RMV_TILE) {
+        const T al = (T)a / (T)npts + uoff;
+        auto sqd = [&](int ax, int64_t ia) -> T {
+          T dv = reinterpret_cast<const T*>(g.g[ax])[ia] - x[n * d + ax] * al;
+          if (sq) dv = dv / ell;
+          return dv * dv;
+        };
+        T so = 0;
+        if (d == 2) so = sqd(0, o);
+        if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
+        so_s[a] = so;
+        xl_s[a] = x[n * d + d - 1] * al;
+      }
+      __syncthreads();
+      T xn2 = 0;
+      for (int ax = 0; ax < d; ++ax) xn2 += x[n * d + ax] * x[n * d + ax];
+      const T dist = sqrt(xn2);
+      T ka = 0;
+      for (int a = 0; a < npts; ++a) {
+        T dv = ui - xl_s[a];
+        if (sq) dv = dv / ell;
+        const T sv = (d == 1) ? dv * dv : so_s[a] + dv * dv;
+        ka += kern_eval<T>(kind, sv, sig2, ell, kp);
+      }
+      const T kv = ka / (T)npts * dist;
+#pragma unroll
+      for (int s = 0; s < NC; ++s) acc[s] += (double)(kv * cp[s][n]);
+    }
+  } else {
+    const T sinv = (T)1 / (ell * ell);
+    const T sqrt2 = (T)1.4142135623730950488, sqrt2pi = (T)2.5066282746310005024;
+    int64_t oi[2] = {0, 0};
+    if (d == 2) oi[0] = o;
+    if (d == 3) { oi[0] = o / g.m[1]; oi[1] = o % g.m[1]; }
+    T ua[2] = {0, 0};
+    for (int ax = 0; ax < d - 1; ++ax) ua[ax] = reinterpret_cast<const T*>(g.g[ax])[oi[ax]];
+    for (int64_t n = n0; n < n1; ++n) {
+      T xs[3];
+      T av = 0, xn2 = 0;
+      for (int ax = 0; ax < d; ++ax) {
+        const T xv = x[n * d + ax];
+        xs[ax] = xv * sinv;
+        av += xs[ax] * xv;
+        xn2 += xv * xv;
+      }
+      T bo = 0, co = 0;                                       // outer-axis terms of b and c, in axis order
+      for (int ax = 0; ax < d - 1; ++ax) {
+        bo += xs[ax] * ua[ax];
+        co += (ua[ax] * sinv) * ua[ax];
+      }
+      const T dist = sqrt(xn2);
+      const T scale = sqrt((T)1 / av);
+      const T b = (d == 1) ? xs[0] * ui : bo + xs[d - 1] * ui;
+      const T cc = (d == 1) ? (ui * sinv) * ui : co + (ui * sinv) * ui;
+      const T loc = b / av;
+      const T coef = sig2 * exp((b * b) / ((T)2 * av) - cc / (T)2) * sqrt2pi * scale;
+      const T ca = (T)0.5 * ((T)1 + erf(((T)1 - loc) / (scale * sqrt2)));
+      const T cb = (T)0.5 * ((T)1 + erf(((T)0 - loc) / (scale * sqrt2)));
+      const T kv = coef * (ca - cb) * dist;
+#pragma unroll
+      for (int s = 0; s < NC; ++s) acc[s] += (double)(kv * cp[s][n]);
+    }
+  }
+  if (!live) return;
+  const int64_t j = o * inner + i;
+  if (part != nullptr) {
+    double* p = part + slice * NC * M + j;
+#pragma unroll
+    for (int s = 0; s < NC; ++s) p[(int64_t)s * M] = acc[s];
+  } else {
+#pragma unroll
+    for (int s = 0; s < NC; ++s)
+      if (s < ncv) out[(int64_t)s * M + j] = (T)acc[s];
+  }
+}
+
+static int rmv_cus(hipError_t* e) {
+  static int cus[64] = {0};
+  int dev = 0;
+  *e = hipGetDevice(&dev);
+  if (*e != hipSuccess) return 0;
+  if (dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int v = 0;
+    *e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
+    if (*e != hipSuccess) return 0;
+    cus[dev] = v > 0 ? v : 256;
+  }
+  return cus[dev];
+}
+
+// the width of the next group of coefficient rows
+static inline int rmv_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
+
+template <typename T, int KIND>
+static void launch_grid_rmv(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2,
+                            T ell, const T* c, int ncv, int64_t M, int nsplit, int64_t nrun, double* part, T* out) {
+  if (NC == 8)
+    hipLaunchKernelGGL((k_kuf_grid_rmv<T, KIND, 8>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, sig2, ell, c, ncv, M,
+                       nsplit, nrun, part, out);
+  else if (NC == 4)
+    hipLaunchKernelGGL((k_kuf_grid_rmv<T, KIND, 4>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, sig2, ell, c, ncv, M,
+                       nsplit, nrun, part, out);
+  else
+    hipLaunchKernelGGL((k_kuf_grid_rmv<T, KIND, 1>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, sig2, ell, c, ncv, M,
+                       nsplit, nrun, part, out);
+}
+
+template <typename T, int MODE>
+static void launch_semi_rmv(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, int kind,
+                            T sig2, T ell, T kp, int npts, const T* u, const T* c, int ncv, int64_t M, int nsplit,
+                            int64_t nrun, int64_t nchunk, double* part, T* out) {
+  if (NC == 8)
+    hipLaunchKernelGGL((k_kuf_semi_rmv<T, MODE, 8>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, kind, sig2, ell, kp,
+                       npts, u, c, ncv, M, nsplit, nrun, nchunk, part, out);
+  else if (NC == 4)
+    hipLaunchKernelGGL((k_kuf_semi_rmv<T, MODE, 4>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, kind, sig2, ell, kp,
+                       npts, u, c, ncv, M, nsplit, nrun, nchunk, part, out);
+  else
+    hipLaunchKernelGGL((k_kuf_semi_rmv<T, MODE, 1>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, kind, sig2, ell, kp,
+                       npts, u, c, ncv, M, nsplit, nrun, nchunk, part, out);
+}
+
+// mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs >= 0, nc > 0, nsplit >= 0.
+template <typename T>
+static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
+                                const void* xv, int64_t nobs, double sig2, double ell, int npts, const void* uv,
+                                const void* cv, int64_t nc, int64_t nsplit_in, void* outv, hipStream_t s) {
+  KufGrid g{};
+  g.d = ndim;
+  int64_t outer = 1, M = 1;
+  for (int a = 0; a < ndim; ++a) {
+    g.m[a] = m[a];
+    g.g[a] = grids[a];
+    M *= m[a];
+    if (a < ndim - 1) outer *= m[a];
+  }
+  T* out = reinterpret_cast<T*>(outv);
+  if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
+  const T* x = reinterpret_cast<const T*>(xv);
+  const T* c = reinterpret_cast<const T*>(cv);
+  const T* u = reinterpret_cast<const T*>(uv);
+  // the split: a pure function of (nobs, M) and the CU count unless the caller forces it; one
+  // slice whenever the mesh alone gives the blocks that fill the device
+  const int64_t nchunk = (m[ndim - 1] + RMV_TILE - 1) / RMV_TILE;
+  const int64_t ntile = mode == 0 ? (M + RMV_TILE - 1) / RMV_TILE : outer * nchunk;   // blocks per slice
+  const int64_t nrun = (nobs + RMV_RUN - 1) / RMV_RUN;
+  int64_t nsplit = nsplit_in;
+  if (nsplit == 0) {
+    hipError_t e = hipSuccess;
+    const int64_t target = (int64_t)16 * rmv_cus(&e);        // one-wave blocks that fill the device
+    if (e != hipSuccess) return e;
+    nsplit = ntile >= target ? 1 : (target + ntile - 1) / ntile;
+  }
+  if (nsplit > nrun) nsplit = nrun;
+  if (ntile * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
+  const unsigned nb = (unsigned)(ntile * nsplit);
+  double* part = nullptr;
+  if (nsplit > 1) {
+    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part),
+                                  (size_t)nsplit * (size_t)rmv_group(nc) * (size_t)M * sizeof(double), s);
+    if (e != hipSuccess) return e;
+  }
+  for (int64_t s0 = 0; s0 < nc;) {
+    const int NC = rmv_group(nc - s0);
+    const int ncv = (int)(nc - s0 < NC ? nc - s0 : NC);
+    const T* cg = c + s0 * nobs;
+    T* og = out + s0 * M;
+    if (mode == 0) {
+      switch (kind) {
+        case HGP_KERN_SQEXP:
+          launch_grid_rmv<T, HGP_KERN_SQEXP>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
+                                             part, og);
+          break;
+        case HGP_KERN_MATERN12:
+          launch_grid_rmv<T, HGP_KERN_MATERN12>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
+                                                part, og);
+          break;
+        case HGP_KERN_MATERN32:
+          launch_grid_rmv<T, HGP_KERN_MATERN32>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
+                                                part, og);
+          break;
+        default:
+          launch_grid_rmv<T, HGP_KERN_MATERN52>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
+                                                part, og);
+      }
+    } else if (mode == 1) {
+      launch_semi_rmv<T, 1>(NC, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, cg, ncv, M, (int)nsplit,
+                            nrun, nchunk, part, og);
+    } else {
+      launch_semi_rmv<T, 2>(NC, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, cg, ncv, M, (int)nsplit,
+                            nrun, nchunk, part, og);
+    }
+    if (part != nullptr) {
+      const int64_t tot = M * ncv;
+      hipLaunchKernelGGL((k_kuf_rmv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
+                         (int)nsplit, M, NC, ncv, og);
+    }
+    s0 += ncv;
+  }
+  hipError_t e = hipGetLastError();
+  if (part != nullptr) {
+    const hipError_t f = hipFreeAsync(part, s);
+    if (e == hipSuccess) e = f;
+  }
+  return e;
+}
+
+// launcher behind hgp_kuf_grid_rmatvec / hgp_kuf_semi_mc_rmatvec / hgp_kuf_semi_sqexp_rmatvec
+hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
+                       const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* c,
+                       int64_t nc, int64_t nsplit, void* out, hipStream_t s) {
+  if (dtype == HGP_F32)
+    return kuf_rmatvec_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out, s);
+  return kuf_rmatvec_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out, s);
+}
+
+}  // namespace hgp

@@ -15,6 +15,9 @@ hgp_kuf_*_grad, which recomputes K instead of keeping the broadcast for autograd
 Products with Knm that never store it, `kuf_grid_matvec` / `kuf_semi_mc_matvec` /
 `kuf_semi_sqexp_matvec` (hgp_kuf_*_matvec): Knm @ W^T for a few weight rows W, what the posterior
 mean and draws at many points need once K^-1 R v is solved (`ToeplitzInducingGP.predict_mean`).
+Their transposes, `kuf_grid_rmatvec` / `kuf_semi_mc_rmatvec` / `kuf_semi_sqexp_rmatvec`
+(hgp_kuf_*_rmatvec): C @ Knm for a few coefficient rows C, the other half of the matrix-free
+operator K + Knm^T diag(iv) Knm behind `ToeplitzInducingGP.fit_mean`.
 """
 import ctypes
 
@@ -207,6 +210,85 @@ def kuf_semi_sqexp_matvec(kernel, xgrids, x, params, W, nsplit=0):
     check(lib().hgp_kuf_semi_sqexp_matvec(_lib.dtype_code(x.dtype), len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
                                           x.shape[0], s2, el, ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
                                           ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+# ---- products with the transposed cross covariances, Knm never stored (hgp_kuf_*_rmatvec) -------
+
+def _rmatvec_coefs(C, x):
+    """C as contiguous (nc, nobs) rows on x's device in x's dtype, or None where the product
+    declines (C carries a graph that the kernel would drop)."""
+    if torch.is_grad_enabled() and C.requires_grad:
+        return None
+    C = C.detach()
+    if C.dim() == 1:
+        C = C[None, :]
+    if C.dim() != 2 or C.shape[1] != x.shape[0]:
+        raise ValueError(f"C must be (nc, nobs) or (nobs,) with nobs = {x.shape[0]}, got {tuple(C.shape)}")
+    return C.to(device=x.device, dtype=x.dtype).contiguous()
+
+
+def kuf_grid_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
+    """C @ kuf_grid(...) as an (nc, M) tensor without the (nobs, M) matrix (hgp_kuf_grid_rmatvec):
+    C is (nc, nobs) or (nobs,).  nsplit: slices of the observations summed apart (0: the library's
+    choice).  None under the rules by which `kuf_grid` declines."""
+    a = _grid_call_args(kernel, xgrids, x, params)
+    if a is None:
+        return None
+    kind, s2, el, grids, xc, M = a
+    Cc = _rmatvec_coefs(C, x)
+    if Cc is None:
+        return None
+    out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(grids)
+    check(lib().hgp_kuf_grid_rmatvec(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
+                                     ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el,
+                                     ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
+                                     ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_semi_mc_rmatvec(kernel, xgrids, x, params, npts, u=None, C=None, nsplit=0):
+    """C @ kuf_semi_mc(...) as an (nc, M) tensor without the (nobs, M) matrix
+    (hgp_kuf_semi_mc_rmatvec); the offset draw `u` as in `kuf_semi_mc`."""
+    a = _grid_call_args(kernel, xgrids, x, params, gneiting=True)
+    if a is None:
+        return None
+    kind, s2, el, grids, xc, M = a
+    if C is None:
+        raise TypeError("kuf_semi_mc_rmatvec needs the coefficient rows C")
+    Cc = _rmatvec_coefs(C, x)
+    if Cc is None:
+        return None
+    if u is None:
+        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
+    u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
+    out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(grids)
+    kp = float(getattr(kernel, "alpha", 1.))
+    check(lib().hgp_kuf_semi_mc_rmatvec(_lib.dtype_code(x.dtype), kind, kp, len(grids), m, ptrs,
+                                        ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el, int(npts),
+                                        ctypes.c_void_p(u.data_ptr()), ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0],
+                                        int(nsplit), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_semi_sqexp_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
+    """C @ kuf_semi_sqexp(...) as an (nc, M) tensor without the (nobs, M) matrix
+    (hgp_kuf_semi_sqexp_rmatvec); SqExp only, like the forward."""
+    a = _grid_call_args(kernel, xgrids, x, params)
+    if a is None or a[0] != _lib.KERN_SQEXP:
+        return None
+    kind, s2, el, grids, xc, M = a
+    Cc = _rmatvec_coefs(C, x)
+    if Cc is None:
+        return None
+    out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(grids)
+    check(lib().hgp_kuf_semi_sqexp_rmatvec(_lib.dtype_code(x.dtype), len(grids), m, ptrs,
+                                           ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el,
+                                           ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
+                                           ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
     return out
 
 

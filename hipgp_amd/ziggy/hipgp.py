@@ -26,6 +26,7 @@ UnboundLocalError at `hipgp.py:314` fixed (parity pinned by the oracle restateme
 Not built (OUT of the hot path): the full-rank variational family
 (`FullRankToeplitzGP`, `hipgp.py:693-797`: a dense M' x M' covariance, 70 TB at C2).
 """
+import collections
 import os
 
 import numpy as np
@@ -36,6 +37,9 @@ from hipgp_amd.ziggy.misc.toeplitz_tensor import ToeplitzTensor
 from hipgp_amd.ziggy.svi_gp import SviGP
 
 LN_2PI = float(np.log(2 * np.pi))
+
+# what `ToeplitzInducingGP.fit_mean` returns
+MeanFit = collections.namedtuple("MeanFit", ["weights", "qm", "iters", "relres"])
 
 
 def diag_kl_to_standard(m, S):
@@ -395,8 +399,9 @@ class ToeplitzInducingGP(SviGP):
     # does not depend on x: one single-RHS solve, then a product with Knm that never stores it
     # (hgp_kuf_*_matvec).  `predict` solves once per point (`hipgp.py:416-446`); it stays as it is
     # and still owns the predictive sd, which needs those solves.
-    _NO_MEAN_WEIGHTS = ("mean_weights / predict_mean / predict_draws need whitened_type='ziggy': they solve "
-                        "K alpha = R v with the Toeplitz operators, and cholesky whitening has no circulant R")
+    _NO_MEAN_WEIGHTS = ("mean_weights / predict_mean / predict_draws / fit_mean need whitened_type='ziggy': they "
+                        "solve with the Toeplitz operators (K alpha = R v; (K + Kuf^T Sigma^-1 Kuf) beta = "
+                        "Kuf^T Sigma^-1 y, qm = R^T beta), and cholesky whitening has no circulant R")
 
     def variational_draws(self, n, eps=None, generator=None):
         """(n, M') rows v_s = qm + S^{1/2} eps_s of the whitened variational posterior on the device;
@@ -480,6 +485,156 @@ class ToeplitzInducingGP(SviGP):
             mu = self._kuf_product(x, weights.reshape(-1, self.M)[:1], integrated_obs, semi_integrated_estimator,
                                    semi_integrated_samps, mc_offset, batch_size)
             return mu.reshape(-1, 1).cpu().detach()
+
+    # ---- the optimal variational mean of ALL observations from one matrix-free solve -------------
+    # m* = (I + sum_n iv_n kn_n kn_n^T)^-1 sum_n iv_n y_n kn_n (`batch_solve`) equals R^T beta with
+    #   (K + Kuf^T diag(iv) Kuf) beta = Kuf^T (iv o y)
+    # by the push-through identity and R R^T = K: one SPD M x M system whose operator is a K
+    # matvec, a product Kuf p (hgp_kuf_*_matvec) and a product Kuf^T c (hgp_kuf_*_rmatvec); no kn,
+    # no per-observation solve, no dense M' x M' matrix.  beta is also the weight row
+    # `predict_mean(x, weights=...)` takes: K^-1 R qm = K^-1 R R^T beta = beta.
+    _FIT_MEAN_SWEEPS = 4      # fp32 models: sweeps of the recurrence between fp64 residuals (`fit_mean`)
+
+    def _kuf_rproduct(self, x, C, integrated_obs, estimator, samps, mc_offset, batch_size):
+        """C Knm(x), (nc, M) on the device, for coefficient rows C (nc, N): the twin of
+        `_kuf_product`.  The fused products of `hipgp_amd.kuf` where they apply (Knm never stored),
+        else the sum of `C[:, piece] @ _make_grams(piece)[0]` over pieces of `batch_size`
+        observations (None: a piece whose Knm stays under 256 MiB)."""
+        from hipgp_amd import kuf
+        params = self.get_kernel_params()
+        out = None
+        if not integrated_obs:
+            out = kuf.kuf_grid_rmatvec(self.kernel, self.xgrids, x, params, C)
+        elif estimator == "analytic":
+            out = kuf.kuf_semi_sqexp_rmatvec(self.kernel, self.xgrids, x, params, C)
+        elif estimator == "mc-biased":
+            out = kuf.kuf_semi_mc_rmatvec(self.kernel, self.xgrids, x, params, samps, u=mc_offset, C=C)
+        if out is not None:
+            return out
+        if batch_size is None:
+            batch_size = max(1, (256 << 20) // (self.M * x.element_size()))
+        out = C.new_zeros((C.shape[0], self.M))
+        for a in range(0, x.shape[0], int(batch_size)):
+            Knm = self._make_grams(x[a:a + batch_size], integrated_obs=integrated_obs,
+                                   semi_integrated_estimator=estimator, semi_integrated_samps=samps,
+                                   mc_offset=mc_offset)[0]
+            out += C[:, a:a + batch_size].matmul(Knm)
+        return out
+
+    def fit_mean(self, xobs, yobs, noise_std=None, integrated_obs=False, semi_integrated_estimator="analytic",
+                 semi_integrated_samps=10, maxiter=1000, tol=1e-6, Kmm=None, mc_offset=None, batch_size=None,
+                 update=True, callback=None):
+        """The ELBO-optimal variational mean for all observations at once, `batch_solve`'s
+        m* = (I + sum_n iv_n kn_n kn_n^T)^-1 sum_n iv_n y_n kn_n, as qm = R^T beta with
+
+            (K + Kuf^T diag(iv) Kuf) beta = Kuf^T (iv o y),
+
+        solved matrix-free by C^-1-preconditioned CG from beta = 0 (one K matvec, one `_kuf_product`
+        and one `_kuf_rproduct` per iteration; neither kn nor Knm is stored on the fused route, and
+        no M' x M' matrix).  iv = 1 / noise_std^2 per observation when given, else exp(-log_noise2).
+        The optimum does not depend on the variational covariance, which is left alone.
+
+        Stops when |r| < tol |b| or after `maxiter` iterations; `callback(it, relres)` is called
+        each iteration.  An fp32 model on the device runs up to 4 such sweeps: beta, b and the
+        residual between sweeps are fp64 (one fp64 application of the operator per sweep, on an fp64
+        plan built here), each sweep is the fp32 recurrence on the fp64 residual, and it ends when
+        that residual is under tol |b| or `maxiter` iterations are spent in all; R^T is applied in
+        fp64.  Without this the fp32 recurrence stalls near eps cond(A) and the mean is 1e-3 off.  With the "mc-biased" estimator and no `mc_offset` one offset is drawn here
+        and used for every product: CG needs one fixed symmetric operator.
+
+        Returns MeanFit(weights, qm, iters, relres): weights = beta as a (1, M) device row, what
+        `predict_mean(x, weights=...)` takes (K^-1 R qm = beta); qm = R^T beta (M', 1); relres the
+        recurrence's last |r| / |b|.  update=True writes the mean into the model as `batch_solve`
+        does (theta1 = lam qm with lam = -2 theta2 as it stands, or global_m = qm)."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        with torch.no_grad():
+            dev = self.xgrids[0].device
+            if Kmm is None:
+                Kmm = self.toeplitz()
+            x = xobs.to(dev)
+            y = yobs.to(device=dev, dtype=self.dtype).reshape(-1)
+            if noise_std is not None:
+                iv = 1 / noise_std.to(device=dev, dtype=self.dtype).reshape(-1) ** 2
+            else:
+                iv = torch.exp(-self.log_noise2).detach().to(dev).expand(y.shape[0])
+            if integrated_obs and semi_integrated_estimator == "mc-biased" and mc_offset is None:
+                mc_offset = torch.rand(1, dtype=self.kernel.dtype, device=dev)      # kernels.py:28-29
+            route = (integrated_obs, semi_integrated_estimator, semi_integrated_samps, mc_offset, batch_size)
+            if hasattr(Kmm, "set_batch_shape"):
+                Kmm.set_batch_shape((1,))
+
+            def operator(Kop, xx, ivv):
+                def A(p):
+                    f = self._kuf_product(xx, p, *route).reshape(-1)
+                    return Kop._matmul_by_K(p).reshape(1, self.M) + self._kuf_rproduct(xx, (ivv * f)[None, :], *route)
+                return A
+
+            A = operator(Kmm, x, iv)
+            # fp32 on the device: the recurrence alone stalls near eps * cond(A), and R^T turns that
+            # into 1e-3 of the mean.  So beta, b and the residual between sweeps are kept in fp64
+            # (one fp64 application of the operator per sweep, on a second plan); the iterations stay fp32.
+            refine = self.dtype == torch.float32 and dev.type == 'cuda'
+            if refine:
+                kparams = self.get_kernel_params()
+                K64 = ToeplitzTensor(xgrids=[g.double() for g in self.xgrids],
+                                     kernel=lambda a, c: self.kernel(a, c, params=kparams), batch_shape=None,
+                                     jitter_val=self.jitter_val)
+                K64.set_batch_shape((1,))
+                x64, iv64 = x.double(), iv.double()
+                A64 = operator(K64, x64, iv64)
+                b = self._kuf_rproduct(x64, (iv64 * y.double())[None, :], *route)
+            else:
+                b = self._kuf_rproduct(x, (iv * y)[None, :], *route)
+            beta = torch.zeros_like(b)
+            bnorm = float(torch.linalg.vector_norm(b))
+            it, relres = 0, 0.0
+            if bnorm > 0:
+                relres = 1.0
+                rtrue = b
+                for _ in range(self._FIT_MEAN_SWEEPS if refine else 1):
+                    # one sweep: PCG on A d = rtrue from d = 0, until |r| < tol |b|
+                    r = rtrue.to(self.dtype).clone()
+                    d = torch.zeros_like(r)
+                    z = Kmm._matmul_by_Cinv(r).reshape(1, self.M)
+                    p = z.clone()
+                    rz = torch.sum(r * z)
+                    while it < maxiter:
+                        Ap = A(p)
+                        alpha = rz / torch.sum(p * Ap)
+                        d += alpha * p
+                        r -= alpha * Ap
+                        it += 1
+                        relres = float(torch.linalg.vector_norm(r)) / bnorm
+                        if callback is not None:
+                            callback(it, relres)
+                        if relres < tol:
+                            break
+                        z = Kmm._matmul_by_Cinv(r).reshape(1, self.M)
+                        rz_new = torch.sum(r * z)
+                        p = z + (rz_new / rz) * p
+                        rz = rz_new
+                    beta += d.to(beta.dtype)
+                    if not refine or it >= maxiter:
+                        break
+                    rtrue = b - A64(beta)
+                    if float(torch.linalg.vector_norm(rtrue)) < tol * bnorm:
+                        break
+            if refine:
+                qm = K64._matmul_by_RT(beta).reshape(self.Mprime, 1).to(self.dtype)
+                beta = beta.to(self.dtype)
+            else:
+                qm = Kmm._matmul_by_RT(beta).reshape(self.Mprime, 1)
+            if update:
+                if self.parameterization == 'standard':
+                    self.global_m.data[:] = qm
+                else:
+                    lam = -2 * self.global_theta2.data
+                    if self.name == 'mean-field':
+                        self.global_theta1.data[:] = lam * qm
+                    else:
+                        self.global_theta1.data[:] = self.block_diag_multiply(lam, qm.t()).t()
+            return MeanFit(beta, qm, it, relres)
 
     def predict_draws(self, x, n, eps=None, generator=None, integrated_obs=False,
                       semi_integrated_estimator="analytic", semi_integrated_samps=10, maxiter_cg=50, Kmm=None,

@@ -339,6 +339,48 @@ int hgp_kuf_semi_sqexp_matvec(int dtype, int ndim, const int64_t* m, const void*
                               const void* x, int64_t nobs, double sig2, double ell,
                               const void* w, int64_t nw, int64_t nsplit, void* out, void* hip_stream);
 
+/* Product with the TRANSPOSED point-observation cross covariance, never stored:
+ *   out[s, j] = sum_n Kuf[n, j] c[s, n],   Kuf[n, j] = k(x_n, u_j) exactly as hgp_kuf_grid writes it,
+ *   c: (nc, nobs) rows, out: (nc, M) rows in the PCG layout (mesh order, last axis fastest), both
+ *   device arrays of dtype; x, grids, kind as hgp_kuf_grid (HGP_KERN_GNEITING refused as there).
+ * The arguments mirror hgp_kuf_grid_matvec with (w, nw) replaced by (c, nc).  Together the two give
+ * the operator p -> K p + Kuf^T diag(iv) Kuf p of the system whose solution is the optimal
+ * variational mean of all observations (the closed form hipgp.py:278-368 reaches through kn and a
+ * dense M' x M' solve).
+ * A block is one wave and owns 64 mesh points, one per lane; it sweeps the observations in order, so
+ * everything indexed by the observation is wave-uniform.  Products are summed in dtype over runs of
+ * at most 256 consecutive observations, the runs in fp64 in observation order.  nsplit: slices the
+ * observations are cut into (whole runs of 256), their fp64 partial sums part[slice][s][j] added in
+ * slice order by a second kernel.  0: chosen from (nobs, M) and the device's CU count alone:
+ * 1 when ceil(M / 64) >= 16 CUs, else ceil(16 CUs / ceil(M / 64)); > 0: that many; either way at
+ * most ceil(nobs / 256).  No atomics: the same bits on every call with the same arguments on the
+ * same device.
+ * Scratch, nsplit > 1 only: nsplit * min(nc, 8) * M fp64, stream-ordered (hipMallocAsync /
+ * hipFreeAsync on hip_stream); with nsplit = 0 under 32 MiB at 256 CUs.
+ * nobs = 0: out is set to zero (an empty sum); nc = 0: nothing written; both return 0.  HGP_E_ARG
+ * (before any HIP call): null pointer, bad dtype / kind / ndim, a grid size < 1, nobs / nc /
+ * nsplit < 0.  HGP_E_HIP: the launch or the scratch allocation failed (more than 2^31 - 1 blocks). */
+int hgp_kuf_grid_rmatvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                         const void* x, int64_t nobs, double sig2, double ell,
+                         const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream);
+
+/* The same product with the Monte-Carlo line-integral cross covariance of hgp_kuf_semi_mc: element
+ * values, kind (any HGP_KERN_*), kparam, npts (1..1024, else HGP_E_ARG) and the offset draw u as
+ * there.  A block (one wave) owns one outer mesh index and 64 points of the last axis and walks its
+ * slice of the observations in order; every term is added in fp64.  nsplit, scratch and errors as
+ * hgp_kuf_grid_rmatvec, with outer * ceil(m_last / 64) in place of ceil(M / 64). */
+int hgp_kuf_semi_mc_rmatvec(int dtype, int kind, double kparam, int ndim, const int64_t* m,
+                            const void* const* grids, const void* x, int64_t nobs, double sig2,
+                            double ell, int npts, const void* u, const void* c, int64_t nc,
+                            int64_t nsplit, void* out, void* hip_stream);
+
+/* The same product with the analytic SqExp line integral of hgp_kuf_semi_sqexp: SqExp only like its
+ * forward; an observation with |x_n| = 0 is a NaN row there and makes every out[s, j] NaN, as the
+ * dense product would.  Structure, nsplit, scratch and errors as hgp_kuf_semi_mc_rmatvec. */
+int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void* const* grids,
+                               const void* x, int64_t nobs, double sig2, double ell,
+                               const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream);
+
 /* Doubly-integrated diagonal Knn_diag by table interpolation,
  * KernelDoublyDiagInterpolator.forward (kernels.py:200-220): table = device array of 3*N
  * values in dtype (distance grid, knn, slopes: the reference's float32 table), x: (nobs,

@@ -97,6 +97,19 @@ int main() {
                                 nullptr) == 0);
   EXPECT(hgp_kuf_semi_sqexp_matvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, -2, 0, buf, nullptr) == HGP_E_ARG);
   EXPECT(hgp_kuf_semi_sqexp_matvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, 0, 0, buf, nullptr) == 0);
+  // the transposed Kuf products: refused, or no coefficient rows, before any HIP call
+  EXPECT(hgp_kuf_grid_rmatvec(HGP_F32, HGP_KERN_GNEITING, 2, m3, grids, buf, 3, 1., 1., buf, 2, 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_grid_rmatvec(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., nullptr, 2, 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_grid_rmatvec(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., buf, 2, -1, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_grid_rmatvec(HGP_F32, HGP_KERN_SQEXP, 2, mbad, grids, buf, 3, 1., 1., buf, 2, 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_grid_rmatvec(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 0, 1., 1., buf, 2, 0, nullptr, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_grid_rmatvec(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., nullptr, 0, 0, nullptr, nullptr) == 0);
+  EXPECT(hgp_kuf_semi_mc_rmatvec(HGP_F32, HGP_KERN_GNEITING, 1., 2, m3, grids, buf, 3, 1., 1., 1025, buf, buf, 2, 0, buf,
+                                 nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_semi_mc_rmatvec(HGP_F32, HGP_KERN_GNEITING, 1., 2, m3, grids, buf, 3, 1., 1., 10, buf, buf, 0, 0, buf,
+                                 nullptr) == 0);
+  EXPECT(hgp_kuf_semi_sqexp_rmatvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, -2, 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_kuf_semi_sqexp_rmatvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, 0, 0, buf, nullptr) == 0);
   EXPECT(hgp_knn_doubly_diag(HGP_F32, 2, buf, 3, 1., 1., buf, 1, buf, nullptr) == HGP_E_ARG);
   EXPECT(hgp_knn_doubly_diag(HGP_F32, 2, buf, 0, 1., 1., buf, 50, buf, nullptr) == 0);
   EXPECT(hgp_meanfield_stats(HGP_F32, buf, -1, 16, buf, buf, buf, buf, buf, buf, buf, buf, buf, nullptr) ==

@@ -12,6 +12,7 @@
 #   bench_trim[=ARGS] the bench with HGP_POOL_MB=1024 (idle plans trimmed: per-call re-allocation)
 #   configs           tools/bench_configs.py (five-config table)
 #   phases[=C2,C4]    tools/kn_phases.py --only ...
+#   fitmean[=C2,C5]   tools/fit_mean_time.py --configs ... (transposed Kuf product rates, fit_mean iterations)
 #   passtime=D/B/OP[,D/B/OP...]   tools/passtime.py --dims D --rhs B --op OP (D: 4096x4096)
 #   profile           rocprofv3 --kernel-trace --stats of the bench (tools/profile.sh)
 #   pmc               PMC HBM bytes of the C2 K matvec (tools/pmc_kop.sh)
@@ -66,6 +67,10 @@ EOF
       timeout -k 10 600 python tools/kn_phases.py --only ${arg:-C2,C3,C4,C5} > ${O}_kn_phases.jsonl 2> ${O}_kn_phases.err \
         || fail "$step" $? ${O}_kn_phases.err
       cat ${O}_kn_phases.jsonl ;;
+    fitmean)
+      timeout -k 10 900 python tools/fit_mean_time.py --configs ${arg:-C2,C5} > ${O}_fit_mean_time.jsonl 2> ${O}_fit_mean_time.err \
+        || fail "$step" $? ${O}_fit_mean_time.err
+      cat ${O}_fit_mean_time.jsonl ;;
     passtime)
       for spec in ${arg//,/ }; do
         IFS=/ read -r dims rhs op <<< "$spec"
