@@ -36,6 +36,7 @@ EXPORTS = (
     "hgp_rt_block_stats", "hgp_kuf_grid_grad", "hgp_kuf_semi_mc_grad", "hgp_kuf_semi_sqexp_grad",
     "hgp_kuf_grid_matvec", "hgp_kuf_semi_mc_matvec", "hgp_kuf_semi_sqexp_matvec",
     "hgp_kuf_grid_rmatvec", "hgp_kuf_semi_mc_rmatvec", "hgp_kuf_semi_sqexp_rmatvec",
+    "hgp_plan_is_separable", "hgp_separable_detect",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -76,6 +77,9 @@ def lib():
         "hgp_version": (ctypes.c_char_p, []),
         "hgp_toeplitz_apply_pass": (i32, [vp, i32, vp, vp, i64, i32]),
         "hgp_op_pass_count": (i32, [vp]),
+        "hgp_plan_is_separable": (i32, [vp, ctypes.POINTER(dbl), ctypes.POINTER(dbl)]),
+        "hgp_separable_detect": (i32, [i32, i64, i64, vp, dbl, ctypes.POINTER(dbl), ctypes.POINTER(dbl),
+                                       ctypes.POINTER(dbl)]),
         "hgp_pcg_rnorm2": (i32, [vp, vp]),
         "hgp_kuf_grid": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp]),
         "hgp_kuf_semi_mc": (i32, [i32, i32, dbl, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, i32, vp, vp, vp]),

@@ -10,6 +10,8 @@
 
 #include "../../include/hipgp.h"
 #include "hgp_internal.hpp"
+#include "hgp_sep.hpp"
+#include "hgp_sep_host.hpp"
 
 using namespace hgp;
 
@@ -167,6 +169,20 @@ struct hgp_plan {
   // interleaved on one box (C3 PCG(20) 391 vs 390 ms, C4 209 vs 209 ms, C3 / C4 K op +-0.3 %;
   // profiles/r6i_balanced_chunks_ab_interleaved.jsonl) -- the fixed Qc-sized chunks stay
   bool balanced_chunks = false;
+  // Product-form K matvec (hgp_sep.hpp).  A 2-D column that set_column finds to be
+  // t0[i] t1[j] + sigma [i = j = 0] (and whose spectrum nothing was clamped in, so that K is the
+  // column's own Toeplitz matrix) runs the plain HGP_OP_K apply as two 1-D passes on real data;
+  // the PCG's fused K p, C^-1, R and R^T keep the general passes.  HGP_SEPARABLE=0 (read by every
+  // set_column): never.
+  bool sep_allowed = true;
+  bool separable = false;
+  // set_column queued the device scan of its column; the read-back, the decision and the two
+  // spectra wait for the first plain K matvec or query (sep_resolve), so that a plan which only
+  // ever solves (compute_kn: set-up + PCG + R^T) pays four small launches and no synchronisation
+  bool sep_pending = false;
+  double sep_sigma = 0, sep_k00 = 0, sep_resid = 0;
+  DevBuf sepS0, sepS1;                    // the two real 1-D spectra (L_K[0], L_K[1] values)
+  DevBuf sepW;                            // set-up: 4 words + m0 + m1 + 2 doubles (sep_detect_dev)
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   // hipGraph of a repeated hgp_toeplitz_apply (same op, buffers, RHS count, workspaces, stream):
@@ -180,10 +196,12 @@ struct hgp_plan {
     // every plan-owned buffer an op's launches address (workspaces, the full-grid route's
     // buffers, the spectra): a reallocation of any of them -- e.g. R^T on a grid_k plan growing
     // gridA / gridB past K's size -- must invalidate a captured graph
-    static constexpr int NB = 10;
+    static constexpr int NB = 12;
     const void* buf[NB] = {};
+    bool sep = false;                     // the product-form path (hgp_plan::separable) was on
+    double sigma = 0;                     // its jitter: a by-value kernel argument of the captured launches
     bool operator==(const ApplyKey& o) const {
-      if (!(op == o.op && x == o.x && y == o.y && nrhs == o.nrhs && stream == o.stream)) return false;
+      if (!(op == o.op && x == o.x && y == o.y && nrhs == o.nrhs && stream == o.stream && sep == o.sep && sigma == o.sigma)) return false;
       for (int i = 0; i < NB; ++i)
         if (buf[i] != o.buf[i]) return false;
       return true;
@@ -191,8 +209,10 @@ struct hgp_plan {
   };
   void key_buffers(ApplyKey& k) const {
     const DevBuf* b[ApplyKey::NB] = {&ws1, &ws2, &gridA, &gridB, &specK, &specI, &specR, &specRg, &specKg,
-                                     &specR2};
+                                     &specR2, &sepS0, &sepS1};
     for (int i = 0; i < ApplyKey::NB; ++i) k.buf[i] = b[i]->ptr;
+    k.sep = separable;
+    k.sigma = separable ? sep_sigma : 0;
   }
   ApplyKey last_apply, graph_key;
   hipGraphExec_t graph_exec = nullptr;
@@ -213,7 +233,8 @@ struct hgp_plan {
       bsPre[a].release(); bsPost[a].release(); bsFilt[a].release();
     }
     DevBuf* bufs[] = {&specK, &specI, &specR, &specR2, &specRg, &specKg, &gridA, &gridB, &Dm3, &nclamp, &ws1, &ws2, &set1, &set2, &setM1, &setM2, &setC,
-                      &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn, &st_lam};
+                      &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn, &st_lam,
+                      &sepS0, &sepS1, &sepW};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 3; ++i) {
       if (side[i]) (void)hipStreamDestroy(side[i]);
@@ -440,10 +461,122 @@ bool rt_stats_fused(const hgp_plan* P) {
   return rowt_fits<T>((int)(P->LR[2] / 2), 0) != 0 && linet_fits<T>((int)(P->LR[1] / 2)) != 0;
 }
 
+// ---- product-form K matvec (hgp_sep.hpp) --------------------------------------------
+// row pitch of the real intermediate V[q][i1][i0]: whole 128-B segments per position
+int64_t sep_pitch(const hgp_plan* P) { return round_up(P->m[0], 32); }
+
+// whether set_column tests this plan's columns for the product form at all: 2-D pass plans whose
+// two line lengths have a k_sep_pass and whose per-RHS windows take 32-bit byte offsets
+template <typename T>
+bool sep_candidate(const hgp_plan* P) {
+  if (!P->sep_allowed || P->d != 2 || P->grid_k) return false;
+  if (sep_pairs<T>((int)(P->LK[0] / 2)) == 0 || sep_pairs<T>((int)(P->LK[1] / 2)) == 0) return false;
+  const int64_t lim = (int64_t)1 << 31, es = (int64_t)sizeof(T);
+  return P->m[1] * sep_pitch(P) * es < lim && P->M * es < lim && 128 * std::max(sep_pitch(P), P->m[1]) * es < lim;
+}
+
+// the pending product-form test of the last set_column (hgp_plan::sep_pending): read the device
+// scan (sep_detect_dev) and the clamp count, decide, and build the two real 1-D spectra on the
+// host in fp64 (two transforms of L_K[a] points).  Synchronises the plan's stream.
+template <typename T>
+int sep_finish(hgp_plan* P) {
+  const int64_t m0 = P->m[0], m1 = P->m[1];
+  std::vector<double> h((size_t)(4 + m0 + m1 + 2));
+  unsigned long long nclamped = 0;
+  HIP_TRY(hipMemcpyAsync(h.data(), P->sepW.ptr, h.size() * sizeof(double), hipMemcpyDeviceToHost, P->stream));
+  HIP_TRY(hipMemcpyAsync(&nclamped, P->nclamp.ptr, sizeof(nclamped), hipMemcpyDeviceToHost, P->stream));
+  HIP_TRY(hipStreamSynchronize(P->stream));
+  unsigned long long w[4];
+  std::memcpy(w, h.data(), sizeof(w));
+  double cmax, best, rmax;
+  std::memcpy(&cmax, &w[0], 8); std::memcpy(&best, &w[1], 8); std::memcpy(&rmax, &w[3], 8);
+  const double* t = h.data() + 4;
+  const double k00 = t[m0 + m1], sigma = t[m0 + m1 + 1];
+  const bool ok = sep_accept(cmax, best, k00, sigma, rmax, sep_eps(P->dtype), sep_tiny(P->dtype));
+  P->sep_k00 = k00;
+  P->sep_sigma = sigma;
+  P->sep_resid = cmax > 0 ? rmax / cmax : 0;
+  // a clamped spectrum is not the column's own Toeplitz matrix any more: the general passes
+  if (!ok || nclamped != 0) return 0;
+  for (int ax = 0; ax < 2; ++ax) {
+    const int64_t m = ax == 0 ? m0 : m1, L = P->LK[ax];
+    const std::vector<double> s = sep_spectrum(std::vector<double>(t + (ax == 0 ? 0 : m0), t + (ax == 0 ? 0 : m0) + m), L);
+    std::vector<T> sT((size_t)L);
+    for (int64_t k = 0; k < L; ++k) sT[(size_t)k] = (T)s[(size_t)k];
+    DevBuf& buf = ax == 0 ? P->sepS0 : P->sepS1;
+    HGP_TRY(buf.ensure((size_t)L * sizeof(T)));
+    HIP_TRY(hipMemcpyAsync(buf.ptr, sT.data(), (size_t)L * sizeof(T), hipMemcpyHostToDevice, P->stream));
+    HIP_TRY(hipStreamSynchronize(P->stream));   // sT is a temporary
+  }
+  P->separable = true;
+  return 0;
+}
+
+// y = K x as T0 X T1^T + sigma X: pass 0 along axis 1 into the real workspace V[q][i1][i0], pass 1
+// along axis 0 back into y in the (B, M) order, adding sigma x.  RHS chunks on the plan's streams
+// as run_op; the workspace is ws1 (nrhs-chunk x m1 x pitch real values per stream).
+template <typename T>
+int run_sep(hgp_plan* P, const void* x, void* y, int64_t nrhs, const int* done) {
+  const int64_t m0 = P->m[0], m1 = P->m[1], PV = sep_pitch(P);
+  const int64_t per = m1 * PV * (int64_t)sizeof(T);
+  const int NS = (int)std::min<int64_t>(std::max(1, P->nstreams), nrhs);
+  int64_t Qc = std::max<int64_t>(1, std::min<int64_t>((nrhs + NS - 1) / NS, P->ws_budget / (per * NS)));
+  // chunks whose intermediate stays in the Infinity Cache between the two passes, as run_op's
+  if (!P->ws_explicit && per * 8 <= ((int64_t)72 << 20)) Qc = std::min<int64_t>(Qc, 8);
+  HGP_TRY(P->ws1.ensure((size_t)(per * Qc * NS)));
+  hipStream_t streams[4] = {P->stream, nullptr, nullptr, nullptr};
+  if (NS > 1) {
+    HGP_TRY(ensure_side_streams(P, NS));
+    HIP_TRY(hipEventRecord(P->ev_fork, P->stream));
+    for (int i = 1; i < NS; ++i) {
+      streams[i] = P->side[i - 1];
+      HIP_TRY(hipStreamWaitEvent(streams[i], P->ev_fork, 0));
+    }
+  }
+  const T* xin = reinterpret_cast<const T*>(x);
+  T* yout = reinterpret_cast<T*>(y);
+  const int64_t nch = (nrhs + Qc - 1) / Qc;
+  for (int64_t chunk = 0; chunk < nch; ++chunk) {
+    const int64_t q0 = chunk * Qc;
+    const int qn = (int)(std::min(nrhs, q0 + Qc) - q0);
+    const int slot = (int)(chunk % NS);
+    hipStream_t st = streams[slot];
+    T* V = reinterpret_cast<T*>(P->ws1.ptr) + (int64_t)slot * Qc * m1 * PV;
+    auto run = [&](int H, const SepDesc& D) -> int {
+      hipError_t e = launch_sep<T>(H, D, st);
+      if (e != hipSuccess) return fail(HGP_E_HIP, std::string("k_sep_pass launch: ") + hipGetErrorString(e));
+      return 0;
+    };
+    SepDesc A;
+    std::memset(&A, 0, sizeof(A));
+    A.in = xin + q0 * P->M; A.in_q = P->M; A.in_r = m1; A.in_len = (int)m1; A.nrows = (int)m0;
+    A.out = V; A.out_q = m1 * PV; A.out_p = PV; A.out_len = (int)m1;
+    A.spec = P->sepS1.ptr; A.tw = P->twK[1].ptr; A.Q = qn; A.Rn = (int)((m0 + 1) / 2); A.done = done;
+    HGP_TRY(run((int)(P->LK[1] / 2), A));
+    SepDesc B;
+    std::memset(&B, 0, sizeof(B));
+    B.in = V; B.in_q = m1 * PV; B.in_r = PV; B.in_len = (int)m0; B.nrows = (int)m1;
+    B.out = yout + q0 * P->M; B.out_q = P->M; B.out_p = m1; B.out_len = (int)m0;
+    B.add = P->sep_sigma != 0 ? xin + q0 * P->M : nullptr; B.sigma = P->sep_sigma;
+    B.spec = P->sepS0.ptr; B.tw = P->twK[0].ptr; B.Q = qn; B.Rn = (int)((m1 + 1) / 2); B.done = done;
+    HGP_TRY(run((int)(P->LK[0] / 2), B));
+  }
+  for (int i = 1; i < NS; ++i) {
+    HIP_TRY(hipEventRecord(P->ev_join[i - 1], streams[i]));
+    HIP_TRY(hipStreamWaitEvent(P->stream, P->ev_join[i - 1], 0));
+  }
+  return 0;
+}
+
 template <typename T>
 int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void* dotv, void* partial,
            const int* done, int only_pass = -1, void* spart = nullptr, const RowEpi* epi = nullptr,
            const MidFn* mid = nullptr, const PairOp* pair = nullptr, const RowStats* stats = nullptr) {
+  // the plain K matvec of a product-form plan; the fused forms (dots, PCG epilogues) stay general,
+  // and so does the pass split (hgp_toeplitz_apply_pass times the general sequence's three passes)
+  if (op == HGP_OP_K && P->separable && only_pass < 0 && dotv == nullptr && partial == nullptr && spart == nullptr &&
+      epi == nullptr && mid == nullptr && pair == nullptr && stats == nullptr)
+    return run_sep<T>(P, x, y, nrhs, done);
   if (grid_route(P, op)) {
     if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "internal: HGP_OP_RSQ has no full-grid route");
     if (spart != nullptr || epi != nullptr || mid != nullptr || only_pass >= 0 || stats != nullptr)
@@ -1179,6 +1312,23 @@ int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_mi
   double* b = reinterpret_cast<double*>(P->setM2.ptr);
   to_f64<T>(column, a, M, jitter, s);
   P->clamp_min = clamp_min;
+  // product-form test of the column (before the transforms below overwrite it); read at the end
+  // a captured K matvec holds values of the previous column (the product form's sigma and whether
+  // sigma x is added at all are kernel arguments, not buffer contents): never replay it
+  P->drop_graph();
+  P->last_apply = hgp_plan::ApplyKey();
+  // the knob is read per column, so a pooled plan follows the environment of its current user
+  const char* sp = std::getenv("HGP_SEPARABLE");
+  P->sep_allowed = !(sp && std::atoi(sp) == 0);
+  const bool sep_try = sep_candidate<T>(P);
+  P->sep_pending = sep_try;
+  P->separable = false;
+  P->sep_sigma = P->sep_k00 = P->sep_resid = 0;
+  if (sep_try) {
+    HGP_TRY(P->sepW.ensure((size_t)(4 + P->m[0] + P->m[1] + 2) * sizeof(double)));
+    unsigned long long* w = reinterpret_cast<unsigned long long*>(P->sepW.ptr);
+    sep_detect_dev(a, P->m[0], P->m[1], w, reinterpret_cast<double*>(w + 4), s);
+  }
   // D_raw = DCT-I over every axis (length-n FFT of the circulant embedding, real part)
   for (int ax = 0; ax < d; ++ax) {
     HGP_TRY(dct_axis(P, ax, a, b, 1, 1.0));
@@ -1738,6 +1888,16 @@ int check_plan(const hgp_plan* P) {
   return 0;
 }
 
+int use_device(const hgp_plan* P);
+
+// settle a pending product-form test (hgp_plan::sep_pending); not inside a stream capture
+int sep_resolve(hgp_plan* P) {
+  if (!P->sep_pending) return 0;
+  HGP_TRY(use_device(P));
+  P->sep_pending = false;
+  return DISPATCH(P, sep_finish, P);
+}
+
 int use_device(const hgp_plan* P) {
   HIP_TRY(hipSetDevice(P->device));
   return 0;
@@ -1908,6 +2068,8 @@ int hgp_toeplitz_apply(hgp_plan* plan, int op, const void* x, void* y, int64_t n
                                "run inside a stream capture");
     HGP_TRY(DISPATCH(plan, ensure_rsq_t, plan));
   }
+  // (a caller that is capturing leaves the test pending: its K matvec takes the general passes)
+  if (op == HGP_OP_K && cst == hipStreamCaptureStatusNone) HGP_TRY(sep_resolve(P));
   hgp_plan::ApplyKey key;
   key.op = op; key.x = x; key.y = y; key.nrhs = nrhs; key.stream = P->stream;
   P->key_buffers(key);
@@ -2019,12 +2181,37 @@ int hgp_toeplitz_apply_pass(hgp_plan* plan, int op, const void* x, void* y, int6
   if (op < HGP_OP_K || op > HGP_OP_R || pass < -1) return fail(HGP_E_ARG, "bad op/pass");
   if (nrhs <= 0 || x == nullptr || y == nullptr || x == y) return fail(HGP_E_ARG, "bad x/y/nrhs");
   HGP_TRY(use_device(plan));
+  if (op == HGP_OP_K && pass < 0) HGP_TRY(sep_resolve(plan));
   return DISPATCH(plan, run_op, plan, op, x, y, nrhs, nullptr, nullptr, nullptr, pass);
 }
 
 int hgp_op_pass_count(const hgp_plan* plan) {
   if (plan == nullptr) return fail(HGP_E_ARG, "null plan");
   return plan->d == 1 ? 1 : (plan->d == 2 ? 3 : 5);
+}
+
+int hgp_plan_is_separable(hgp_plan* plan, double* sigma, double* resid) {
+  HGP_TRY(check_plan(plan));
+  if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  HGP_TRY(sep_resolve(plan));
+  if (sigma) *sigma = plan->sep_sigma;
+  if (resid) *resid = plan->sep_resid;
+  return plan->separable ? 1 : 0;
+}
+
+int hgp_separable_detect(int dtype, int64_t m0, int64_t m1, const void* column, double jitter, double* out4,
+                         double* t0, double* t1) {
+  if (column == nullptr || out4 == nullptr || m0 < 1 || m1 < 1) return fail(HGP_E_ARG, "hgp_separable_detect: bad argument");
+  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
+  std::vector<double> c((size_t)(m0 * m1));
+  for (int64_t i = 0; i < m0 * m1; ++i)
+    c[(size_t)i] = dtype == HGP_F32 ? (double)static_cast<const float*>(column)[i] : static_cast<const double*>(column)[i];
+  c[0] += jitter;
+  const SepFactors f = sep_detect(c.data(), m0, m1, sep_eps(dtype), sep_tiny(dtype));
+  out4[0] = f.ok ? 1.0 : 0.0; out4[1] = f.sigma; out4[2] = f.resid; out4[3] = f.k00;
+  if (t0 != nullptr && !f.t0.empty()) std::copy(f.t0.begin(), f.t0.end(), t0);
+  if (t1 != nullptr && !f.t1.empty()) std::copy(f.t1.begin(), f.t1.end(), t1);
+  return 0;
 }
 
 int hgp_pcg_begin(hgp_plan* plan, const void* b, void* x, int64_t nrhs, int use_precond, int layout) {
@@ -2687,7 +2874,7 @@ int hgp_plan_mem(const hgp_plan* plan, int64_t* scratch_bytes, int64_t* table_by
       b += (int64_t)(plan->twK[a].bytes + plan->twR[a].bytes + plan->tw64K[a].bytes + plan->tw64R[a].bytes +
                      plan->bsPre[a].bytes + plan->bsPost[a].bytes + plan->bsFilt[a].bytes);
     b += (int64_t)(plan->specK.bytes + plan->specI.bytes + plan->specR.bytes + plan->specRg.bytes + plan->specKg.bytes +
-                   plan->Dm3.bytes + plan->specR2.bytes);
+                   plan->Dm3.bytes + plan->specR2.bytes + plan->sepS0.bytes + plan->sepS1.bytes);
     *table_bytes = b;
   }
   return 0;

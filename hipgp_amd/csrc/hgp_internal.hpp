@@ -30,6 +30,11 @@ template <typename T> int rowt_group(int H);
 template <typename T>
 hipError_t launch_linet(int H, int inv, const PassDesc& d, hipStream_t s);
 template <typename T> int linet_fits(int H);
+// product-form K matvec (hgp_sep.hpp): one axis pass of H = L / 2 points; sep_pairs: row pairs per
+// block, 0 where the length has no such kernel
+struct SepDesc;
+template <typename T> hipError_t launch_sep(int H, const SepDesc& d, hipStream_t s);
+template <typename T> int sep_pairs(int H);
 
 // setup (fp64)
 // Bluestein partial DFT pieces of the DCT-I (hgp_kernels.hip)
@@ -40,6 +45,8 @@ void chirp_post(const double2* c, const double2* post, double* y, int64_t total,
                 hipStream_t s);
 template <typename T> void to_f64(const void* src, double* dst, int64_t n, double add0, hipStream_t s);
 void square_f64(const double* src, double* dst, int64_t n, hipStream_t s);   // dst = src^2 (in place allowed)
+// product-form test of the 2-D column c (hgp_kernels.hip): w = 4 words, t = m0 + m1 + 2 doubles
+void sep_detect_dev(const double* c, int64_t m0, int64_t m1, unsigned long long* w, double* t, hipStream_t s);
 // nclamp[0] counts the clamped entries; nclamp[1] / nclamp[2] receive max D / max 1/D (finite
 // values, as the bits of positive doubles) for pack_scale
 void clamp_spectrum(const double* Draw, double* out3, int64_t M, double clamp_min, unsigned long long* nclamp,

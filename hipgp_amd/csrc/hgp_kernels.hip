@@ -105,6 +105,92 @@ void square_f64(const double* src, double* dst, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_square_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n);
 }
 
+// Product-form test of a 2-D column c (m0 x m1, fp64, jitter on c[0]) on the device -- the
+// arithmetic of sep_detect (hgp_sep_host.hpp), in four small launches:
+//   w[0] = max |c|, w[1] = the largest off-corner |c[i][j]| (i, j >= 1), both as the bits of
+//   non-negative doubles (ordered like unsigned integers); w[2] = the smallest index holding w[1];
+//   t = [t0 (m0) | t1 (m1) | k00 | sigma]; w[3] = max |c[i][j] - t0[i] t1[j]|, corner excluded.
+// NaNs order above every finite value, so a column holding one is refused by the host's test.
+__global__ void k_sep_max(const double* __restrict__ c, int64_t m0, int64_t m1, unsigned long long* w) {
+  const int64_t M = m0 * m1;
+  double a = 0.0, b = 0.0;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
+    const double v = fabs(c[e]);
+    const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
+    if (vb > (unsigned long long)__double_as_longlong(a)) a = v;
+    if (e >= m1 && e % m1 != 0 && vb > (unsigned long long)__double_as_longlong(b)) b = v;
+  }
+  unsigned long long ab = (unsigned long long)__double_as_longlong(a), bb = (unsigned long long)__double_as_longlong(b);
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long a2 = __shfl_xor(ab, off, 64), b2 = __shfl_xor(bb, off, 64);
+    ab = a2 > ab ? a2 : ab;
+    bb = b2 > bb ? b2 : bb;
+  }
+  // one atomic pair per block (a per-wave one serialised on the two words: 97 us at 1M entries)
+  __shared__ unsigned long long wa[4], wb[4];
+  if ((threadIdx.x & 63) == 0) { wa[threadIdx.x >> 6] = ab; wb[threadIdx.x >> 6] = bb; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 4; ++i) { ab = wa[i] > ab ? wa[i] : ab; bb = wb[i] > bb ? wb[i] : bb; }
+    atomicMax(&w[0], ab);
+    atomicMax(&w[1], bb);
+  }
+}
+
+__global__ void k_sep_arg(const double* __restrict__ c, int64_t m0, int64_t m1, unsigned long long* w) {
+  const int64_t M = m0 * m1;
+  const unsigned long long best = w[1];
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x)
+    if (e >= m1 && e % m1 != 0 && (unsigned long long)__double_as_longlong(fabs(c[e])) == best)
+      atomicMin(&w[2], (unsigned long long)e);
+}
+
+__global__ void k_sep_fac(const double* __restrict__ c, int64_t m0, int64_t m1, const unsigned long long* w,
+                          double* __restrict__ t) {
+  const int64_t e = w[2] < (unsigned long long)(m0 * m1) ? (int64_t)w[2] : m1 + 1;
+  const int64_t bi = e / m1, bj = e - bi * m1;
+  const double k00 = c[bi * m1] * c[bj] / c[e];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m0) t[i] = i == 0 ? k00 : c[i * m1];
+  else if (i < m0 + m1) t[i] = i == m0 ? 1.0 : c[i - m0] / k00;
+  else if (i == m0 + m1) t[i] = k00;
+  else if (i == m0 + m1 + 1) t[i] = c[0] - k00;
+}
+
+__global__ void k_sep_res(const double* __restrict__ c, int64_t m0, int64_t m1, const double* __restrict__ t,
+                          unsigned long long* w) {
+  const int64_t M = m0 * m1;
+  unsigned long long rb = 0;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
+    if (e == 0) continue;
+    const int64_t i = e / m1, j = e - i * m1;
+    const unsigned long long vb = (unsigned long long)__double_as_longlong(fabs(c[e] - t[i] * t[m0 + j]));
+    rb = vb > rb ? vb : rb;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long r2 = __shfl_xor(rb, off, 64);
+    rb = r2 > rb ? r2 : rb;
+  }
+  __shared__ unsigned long long wr[4];
+  if ((threadIdx.x & 63) == 0) wr[threadIdx.x >> 6] = rb;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 4; ++i) rb = wr[i] > rb ? wr[i] : rb;
+    atomicMax(&w[3], rb);
+  }
+}
+
+void sep_detect_dev(const double* c, int64_t m0, int64_t m1, unsigned long long* w, double* t, hipStream_t s) {
+  const int64_t M = m0 * m1;
+  const unsigned nb = (unsigned)std::min<int64_t>(512, (M + 255) / 256);   // 256-thread blocks (the kernels' 4 wave slots)
+  (void)hipMemsetAsync(w, 0, 4 * sizeof(unsigned long long), s);
+  (void)hipMemsetAsync(w + 2, 0xff, sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(k_sep_max, dim3(nb), dim3(256), 0, s, c, m0, m1, w);
+  hipLaunchKernelGGL(k_sep_arg, dim3(nb), dim3(256), 0, s, c, m0, m1, w);
+  hipLaunchKernelGGL(k_sep_fac, dim3((unsigned)((m0 + m1 + 2 + 255) / 256)), dim3(256), 0, s, c, m0, m1, w, t);
+  hipLaunchKernelGGL(k_sep_res, dim3(nb), dim3(256), 0, s, c, m0, m1, t, w);
+}
+
 // D = max(Draw, clamp); write [D | 1/D | sqrt(D)] (3 x M) and count clamped entries; the
 // maxima of D and 1/D (pack_scale) by a grid-stride sweep of <= 1024 blocks, one atomic each per
 // block (one per 256 elements serialised on two words: 97 us at 1M elements)

@@ -145,9 +145,26 @@ int hgp_pcg_solve(hgp_plan* plan, const void* b, void* x, int64_t nrhs, int maxi
 /* Profiling: run only pass `pass` (0-based; -1 = all) of the op's pass sequence (the
  * intermediate workspace is whatever the previous call left).  hgp_op_pass_count returns the
  * number of passes (1 for 1-D, 3 for 2-D, 5 for 3-D).  Used by bench.py to time each kernel
- * with HIP events. */
+ * with HIP events.  On a product-form plan (below) a single pass is still one of the general
+ * sequence's three -- the sequence the fused PCG runs; pass = -1 runs the product form. */
 int hgp_toeplitz_apply_pass(hgp_plan* plan, int op, const void* x, void* y, int64_t nrhs, int pass);
 int hgp_op_pass_count(const hgp_plan* plan);
+
+/* Product form.  hgp_plan_set_column tests every 2-D column for c[i][j] = t0[i] t1[j] + sigma
+ * [i = j = 0] (a product kernel on a product grid plus the jitter); where it holds to the
+ * column's storage rounding and the spectrum clamp changed nothing, hgp_toeplitz_apply(HGP_OP_K)
+ * runs K X = T0 X T1^T + sigma X as two 1-D passes on real data instead of the padded 2-D
+ * transform (the environment variable HGP_SEPARABLE=0, read by every hgp_plan_set_column, turns this off).
+ * hgp_plan_is_separable: 1 if the last column took the product form, 0 if not, a negative HGP_E*
+ * code on error; the decision is made on the first such call or plain K matvec after a set_column
+ * (it synchronises the plan's stream once and must not run inside a stream capture); sigma / resid
+ * (optional) receive the recovered jitter and max |c - t0 t1^T| / max |c|, corner excluded (0
+ * where the plan is not tested: 1-D, 3-D, HGP_SEPARABLE=0).
+ * hgp_separable_detect runs the same test on a HOST column of m0 x m1 values (no device):
+ * out4 = {accepted, sigma, resid, k00}, t0 / t1 (optional, m0 / m1 doubles) the factor columns. */
+int hgp_plan_is_separable(hgp_plan* plan, double* sigma, double* resid);
+int hgp_separable_detect(int dtype, int64_t m0, int64_t m1, const void* column, double jitter, double* out4,
+                         double* t0, double* t1);
 
 /* Stepwise PCG for the callback form of conj_grad/conj_grad2 (cg.py:77-78): begin() sets
  * x0 = 0, r = b, z = P r, p = z; step() runs one iteration and, if `converged` != NULL,
