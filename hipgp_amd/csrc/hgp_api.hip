@@ -2557,6 +2557,34 @@ int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void
   return 0;
 }
 
+int hgp_rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
+                   const void* omega, const void* phase, int64_t nfeat, const void* w, int64_t nw, double scale,
+                   int transposed, double beta, int64_t nsplit, void* out, void* hip_stream) {
+  // all checks before any HIP call
+  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");
+  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
+  if ((x == nullptr) == (grids == nullptr))
+    return fail(HGP_E_ARG, "the points are either x (explicit rows) or grids (the mesh): give exactly one");
+  if (nobs < 0 || nfeat < 0 || nw < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nfeat, nw and nsplit must be >= 0");
+  int64_t npoints = nobs;
+  if (x == nullptr) {
+    if (m == nullptr) return fail(HGP_E_ARG, "mesh mode needs m");
+    npoints = 1;
+    for (int a = 0; a < ndim; ++a) {
+      if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
+      npoints *= m[a];
+    }
+  }
+  if (npoints == 0 || nw == 0) return 0;
+  if (nfeat < 1) return fail(HGP_E_ARG, "nfeat must be >= 1 when there are points");
+  if (omega == nullptr || phase == nullptr || w == nullptr || out == nullptr)
+    return fail(HGP_E_ARG, "null omega / phase / w / out");
+  hipError_t e = rff_matvec(dtype, ndim, m, grids, x, npoints, omega, phase, nfeat, w, nw, scale, transposed != 0, beta,
+                            nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rff_matvec: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_knn_doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* table,
                         int N, void* out, void* hip_stream) {
   if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");

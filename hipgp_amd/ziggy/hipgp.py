@@ -439,9 +439,14 @@ class ToeplitzInducingGP(SviGP):
             if hasattr(Kmm, "set_batch_shape"):
                 Kmm.set_batch_shape((nv,))
             b = Kmm._matmul_by_R(rows).reshape(nv, self.M)
-            if hasattr(Kmm, "inv_matmul_") and b.is_contiguous() and not Kmm.column.requires_grad:
-                return Kmm.inv_matmul_(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
-            return Kmm.inv_matmul(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
+            return self._solve_rows(Kmm, b, maxiter_cg, tol)
+
+    @staticmethod
+    def _solve_rows(Kmm, b, maxiter_cg, tol):
+        """K^-1 b for (nv, M) rows b, no graph: in place of b where `inv_matmul_` allows."""
+        if hasattr(Kmm, "inv_matmul_") and b.is_contiguous() and not Kmm.column.requires_grad:
+            return Kmm.inv_matmul_(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
+        return Kmm.inv_matmul(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
 
     def _kuf_product(self, x, W, integrated_obs, estimator, samps, mc_offset, batch_size):
         """Knm(x) W^T, (N, nw) on the device, for weight rows W (nw, M): the fused products of
@@ -655,6 +660,110 @@ class ToeplitzInducingGP(SviGP):
             alpha = self.mean_weights(v, maxiter_cg=maxiter_cg, Kmm=Kmm)
             out = self._kuf_product(x, alpha, integrated_obs, semi_integrated_estimator, semi_integrated_samps,
                                     mc_offset, batch_size)
+            return out.t().contiguous().cpu().detach()
+
+    # ---- joint draws of f itself at any points: pathwise conditioning -------------------------------
+    # Matheron's rule with a random-Fourier-feature prior.  A draw of the prior everywhere,
+    #   f_prior(x) = sqrt(2 sig2 / F) sum_f w_f cos(omega_f . x + b_f),
+    # is corrected at the inducing points from its own values u_prior = f_prior(U) + sqrt(jitter) xi to
+    # a draw u = R v of the variational posterior:
+    #   f(x) = f_prior(x) + sum_j k(x, u_j) alpha_j,   alpha = K^-1 (u - u_prior).
+    # Its covariance is k(x, x') - k_xU K^-1 k_Ux' + k_xU K^-1 R S R^T K^-1 k_Ux': `predict`'s variance,
+    # ktilde included, up to the feature error of the prior.  Per draw: one right-hand side of the
+    # batched solve, one row of the fused Kuf product and one row of the fused feature product
+    # (hgp_rff_matvec), which also runs once on the whole mesh to form the right-hand side.
+    def _rff_product(self, x, omega, phase, W, scale, transposed=False, out=None, beta=0.0):
+        """scale * cos(p omega^T + phase) W^T for weight rows W (nw, F), (npoints, nw) or transposed
+        (nw, npoints), accumulated into `out` with beta = 1: the part `_kuf_product` plays for Kuf.
+        The points are x, or the inducing mesh when x is None.  The fused product of `hipgp_amd.rff`
+        where it applies (the features never stored), else torch over pieces of points whose
+        (piece, F) features stay under 256 MiB -- CPU stand-ins take that route."""
+        from hipgp_amd import rff
+        if x is None:
+            res = rff.rff_matvec(omega, phase, W, xgrids=self.xgrids, scale=scale, transposed=transposed, out=out,
+                                 beta=beta)
+            pts = self.xinduce
+        else:
+            res = rff.rff_matvec(omega, phase, W, x=x, scale=scale, transposed=transposed, out=out, beta=beta)
+            pts = x
+        if res is not None:
+            return res
+        piece = max(1, (256 << 20) // (omega.shape[0] * pts.element_size()))
+        cols = [scale * W.matmul(torch.cos(pts[a:a + piece].matmul(omega.t()) + phase).t())
+                for a in range(0, pts.shape[0], piece)]
+        acc = torch.cat(cols, dim=1) if cols else W.new_zeros((W.shape[0], 0))         # (nw, npoints)
+        if not transposed:
+            acc = acc.t()
+        if out is None:
+            return acc.contiguous()
+        return out.mul_(beta).add_(acc) if beta != 0 else out.copy_(acc)
+
+    def predict_samples(self, x, n, nfeat=4096, eps=None, features=None, prior_w=None, nugget_eps=None,
+                        generator=None, maxiter_cg=50, Kmm=None, integrated_obs=False):
+        """n joint draws of f ITSELF at the points x, (n, N) on the CPU like `predict_draws`, by
+        pathwise conditioning: f(x) = f_prior(x) + Knm(x) K^-1 (R v - f_prior(U) - sqrt(jitter) xi)
+        with f_prior a random-Fourier-feature draw of the prior and v = qm + S^{1/2} eps
+        (`variational_draws`).  Unlike `predict_draws` the draws carry the residual ktilde = Knn -
+        |kn|^2: their mean is `predict`'s mean and their variance `predict`'s variance.
+
+        One solve of n right-hand sides, one fused Kuf product and two fused feature products (on
+        the inducing mesh for the right-hand side, at x for the result); nothing of size (N, F),
+        (M, F) or (N, M) is stored on the device route.
+
+        ONE feature set (omega, b), `nfeat` features, is shared by all n draws of a call: the prior
+        covariance the draws see differs from k by O(nfeat^-1/2), and that error does not average
+        out over the draws of a call (it does over calls with fresh features).
+
+        Every random input can be given, which makes a call reproducible: eps (n, M') for the
+        variational draw, features = (omega (F, ndim), phase (F)) in radians as
+        `hipgp_amd.rff.spectral_features` returns them, prior_w (n, F) and nugget_eps (n, M)
+        standard normal.  What is not given is drawn with `generator`.  Point observations and
+        whitened_type='ziggy' only (integrated_obs=True raises: the feature prior is a prior of point
+        values); SqExp and Matern kernels with a scalar ell (no Gneiting, no ARD)."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        if integrated_obs:
+            raise NotImplementedError("predict_samples draws f at points: the random-Fourier-feature prior has no "
+                                      "line-integral form here (integrated_obs=True); use predict_draws for the "
+                                      "projected process of line integrals")
+        from hipgp_amd import rff
+        with torch.no_grad():
+            dev = self.xgrids[0].device
+            n = int(n)
+            x = x.to(device=dev, dtype=self.dtype)
+            params = self.get_kernel_params()
+            if features is None:
+                features = rff.spectral_features(self.kernel, params, len(self.xgrids), nfeat, generator=generator,
+                                                 device=dev, dtype=torch.float64)
+            omega, phase = (t.detach().to(device=dev, dtype=torch.float64) for t in features)
+            F = omega.shape[0]
+            if omega.dim() != 2 or omega.shape[1] != len(self.xgrids) or tuple(phase.shape) != (F,) or F < 1:
+                raise ValueError(f"features must be (omega (F, {len(self.xgrids)}), phase (F,)), got "
+                                 f"{tuple(omega.shape)} and {tuple(phase.shape)}")
+
+            def normal(t, shape, name):
+                if t is None:
+                    return torch.randn(shape, generator=generator, dtype=self.dtype, device=dev)
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+                return t.detach().to(device=dev, dtype=self.dtype)
+
+            v = self.variational_draws(n, eps=eps, generator=generator)
+            W = normal(prior_w, (n, F), "prior_w").contiguous()
+            xi = normal(nugget_eps, (n, self.M), "nugget_eps")
+            if x.device.type != "cuda":          # the torch route evaluates the features in the model dtype
+                omega, phase = omega.to(self.dtype), phase.to(self.dtype)
+            scale = float(torch.sqrt(2 * torch.as_tensor(params[0]).detach().double() / F))
+            if Kmm is None:
+                Kmm = self.toeplitz()
+            if hasattr(Kmm, "set_batch_shape"):
+                Kmm.set_batch_shape((n,))
+            b = Kmm._matmul_by_R(v.contiguous()).reshape(n, self.M)
+            b = b.contiguous().sub_(xi, alpha=float(np.sqrt(self.jitter_val)))
+            b = self._rff_product(None, omega, phase, W, -scale, transposed=True, out=b, beta=1.0)
+            alpha = self._solve_rows(Kmm, b, maxiter_cg, 1e-8)
+            out = self._kuf_product(x, alpha, False, "analytic", 10, None, None).contiguous()
+            out = self._rff_product(x, omega, phase, W, scale, out=out, beta=1.0)
             return out.t().contiguous().cpu().detach()
 
 

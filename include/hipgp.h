@@ -398,6 +398,39 @@ int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void
                                const void* x, int64_t nobs, double sig2, double ell,
                                const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream);
 
+/* Product with random Fourier features, never stored:
+ *   acc[i, s] = scale * sum_f w[s, f] cos(2 pi (omega_f . p_i + phase_f)),   out = beta * out + acc,
+ *   omega: (nfeat, ndim) rows and phase: (nfeat), both in REVOLUTIONS (radians / 2 pi; the caller
+ *   divides in fp64 and rounds to dtype), w: (nw, nfeat) rows; all device arrays of dtype.
+ * The points p_i are either the nobs explicit rows of x (nobs, ndim) with grids == NULL (m is not
+ * read), or, with x == NULL, the mesh of the ndim grids in mesh order (last axis fastest, the
+ * coordinates read from grids and m exactly as hgp_kuf_grid reads them; no (M, ndim) array is
+ * built; nobs is not read, npoints = prod m).  Exactly one of x and grids is non-null.
+ * transposed = 0: out is (npoints, nw) rows, like hgp_kuf_grid_matvec; transposed != 0: out is
+ * (nw, npoints) rows, the PCG layout when the points are the mesh.  With beta = 0 out is never read
+ * (it may hold anything, NaN included); beta * out + acc is formed in fp64 and rounded once.
+ * With w standard normal and scale = sqrt(2 sig2 / nfeat), omega drawn from the kernel's spectral
+ * density and phase uniform, acc is a draw of the prior at the points: the prior half of pathwise
+ * conditioning (the reference leaves sample() a TODO, hipgp.py:111-115).
+ * A block owns 64 points, one per lane, and sweeps a slice of the features in order; omega, phase
+ * and w are wave-uniform loads.  fp32 takes the fractional part of the argument and the hardware
+ * cosine (which takes revolutions); fp64 calls cos on 2 pi times the fractional part.  Products are
+ * summed in dtype over runs of at most 256 features, the runs in fp64 in feature order.  nsplit:
+ * slices the features are cut into (whole units of 64), their fp64 partial sums added in slice
+ * order by a second kernel.  0: chosen from (npoints, nfeat) and the device's CU count alone (about
+ * 16 blocks per CU, a slice at least 256 features); > 0: that many, at most ceil(nfeat / 64).  No
+ * atomics: the same bits on every call with the same arguments on the same device.
+ * Scratch, nsplit > 1 only: nsplit * npoints * min(nw, 8) fp64, stream-ordered (hipMallocAsync /
+ * hipFreeAsync on hip_stream).
+ * npoints = 0 or nw = 0: nothing written, 0 returned.  HGP_E_ARG (before any HIP call): x and grids
+ * both given or both null, null m / grids[a] or a grid size < 1 in mesh mode, bad dtype / ndim,
+ * nobs / nfeat / nw / nsplit < 0, nfeat < 1 with points present, null omega / phase / w / out.
+ * HGP_E_HIP: the launch or the scratch allocation failed (more than 2^31 - 1 blocks). */
+int hgp_rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids,
+                   const void* x, int64_t nobs, const void* omega, const void* phase, int64_t nfeat,
+                   const void* w, int64_t nw, double scale, int transposed, double beta,
+                   int64_t nsplit, void* out, void* hip_stream);
+
 /* Doubly-integrated diagonal Knn_diag by table interpolation,
  * KernelDoublyDiagInterpolator.forward (kernels.py:200-220): table = device array of 3*N
  * values in dtype (distance grid, knn, slopes: the reference's float32 table), x: (nobs,

@@ -110,6 +110,14 @@ int main() {
                                  nullptr) == 0);
   EXPECT(hgp_kuf_semi_sqexp_rmatvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, -2, 0, buf, nullptr) == HGP_E_ARG);
   EXPECT(hgp_kuf_semi_sqexp_rmatvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, 0, 0, buf, nullptr) == 0);
+  // the Fourier-feature product: refused or empty before any HIP call
+  EXPECT(hgp_rff_matvec(HGP_F32, 2, nullptr, nullptr, buf, 3, buf, buf, 5, buf, 2, 1., 0, 0., 0, nullptr, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_rff_matvec(HGP_F32, 2, m3, grids, buf, 3, buf, buf, 5, buf, 2, 1., 0, 0., 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_rff_matvec(HGP_F32, 2, nullptr, nullptr, nullptr, 3, buf, buf, 5, buf, 2, 1., 0, 0., 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_rff_matvec(HGP_F32, 2, mbad, grids, nullptr, 0, buf, buf, 5, buf, 2, 1., 1, 1., 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_rff_matvec(HGP_F32, 2, m3, grids, nullptr, 0, buf, buf, 0, buf, 2, 1., 1, 1., 0, buf, nullptr) == HGP_E_ARG);
+  EXPECT(hgp_rff_matvec(HGP_F64, 2, nullptr, nullptr, buf, 0, nullptr, nullptr, 0, nullptr, 2, 1., 0, 0., 0, nullptr, nullptr) == 0);
+  EXPECT(hgp_rff_matvec(HGP_F64, 2, m3, grids, nullptr, 0, buf, buf, 5, nullptr, 0, 1., 1, 1., 0, nullptr, nullptr) == 0);
   EXPECT(hgp_knn_doubly_diag(HGP_F32, 2, buf, 3, 1., 1., buf, 1, buf, nullptr) == HGP_E_ARG);
   EXPECT(hgp_knn_doubly_diag(HGP_F32, 2, buf, 0, 1., 1., buf, 50, buf, nullptr) == 0);
   EXPECT(hgp_meanfield_stats(HGP_F32, buf, -1, 16, buf, buf, buf, buf, buf, buf, buf, buf, buf, nullptr) ==
