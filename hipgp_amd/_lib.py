@@ -36,7 +36,7 @@ EXPORTS = (
     "hgp_rt_block_stats", "hgp_kuf_grid_grad", "hgp_kuf_semi_mc_grad", "hgp_kuf_semi_sqexp_grad",
     "hgp_kuf_grid_matvec", "hgp_kuf_semi_mc_matvec", "hgp_kuf_semi_sqexp_matvec",
     "hgp_kuf_grid_rmatvec", "hgp_kuf_semi_mc_rmatvec", "hgp_kuf_semi_sqexp_rmatvec",
-    "hgp_plan_is_separable", "hgp_separable_detect", "hgp_rff_matvec",
+    "hgp_plan_is_separable", "hgp_separable_detect", "hgp_rff_matvec", "hgp_rff_line_matvec",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -99,6 +99,7 @@ def lib():
                                              vp]),
         "hgp_rff_matvec": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, vp, vp, i64, vp, i64, dbl, i32, dbl, i64,
                                  vp, vp]),
+        "hgp_rff_line_matvec": (i32, [i32, i32, vp, i64, vp, vp, i64, vp, i64, dbl, i32, dbl, i64, vp, vp]),
         "hgp_knn_doubly_diag": (i32, [i32, i32, vp, i64, dbl, dbl, vp, i32, vp, vp]),
         "hgp_meanfield_stats": (i32, [i32, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hgp_meanfield_rowdots": (i32, [i32, vp, i64, i64, vp, vp, vp, vp]),

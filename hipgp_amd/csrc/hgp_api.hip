@@ -2585,6 +2585,24 @@ int hgp_rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* gri
   return 0;
 }
 
+int hgp_rff_line_matvec(int dtype, int ndim, const void* x, int64_t nobs, const void* omega, const void* phase,
+                        int64_t nfeat, const void* w, int64_t nw, double scale, int transposed, double beta,
+                        int64_t nsplit, void* out, void* hip_stream) {
+  // all checks before any HIP call
+  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");
+  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
+  if (x == nullptr) return fail(HGP_E_ARG, "null x: the lines are explicit rows (no mesh mode)");
+  if (nobs < 0 || nfeat < 0 || nw < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nfeat, nw and nsplit must be >= 0");
+  if (nobs == 0 || nw == 0) return 0;
+  if (nfeat < 1) return fail(HGP_E_ARG, "nfeat must be >= 1 when there are lines");
+  if (omega == nullptr || phase == nullptr || w == nullptr || out == nullptr)
+    return fail(HGP_E_ARG, "null omega / phase / w / out");
+  hipError_t e = rff_line_matvec(dtype, ndim, x, nobs, omega, phase, nfeat, w, nw, scale, transposed != 0, beta, nsplit,
+                                 out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rff_line_matvec: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_knn_doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* table,
                         int N, void* out, void* hip_stream) {
   if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");

@@ -113,6 +113,11 @@ hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const
 hipError_t rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t npoints,
                       const void* omega, const void* phase, int64_t nfeat, const void* w, int64_t nw, double scale,
                       int transposed, double beta, int64_t nsplit, void* out, hipStream_t s);
+// out = beta out + scale |x_i| w int_0^1 cos(2 pi (a omega . x_i + phase)) da in closed form (hgp_rff.hip): the line
+// integrals of the same features to the nobs rows of x; nobs > 0, nfeat > 0, nw > 0, nsplit >= 0 (0: chosen here)
+hipError_t rff_line_matvec(int dtype, int ndim, const void* x, int64_t nobs, const void* omega, const void* phase,
+                           int64_t nfeat, const void* w, int64_t nw, double scale, int transposed, double beta,
+                           int64_t nsplit, void* out, hipStream_t s);
 hipError_t meanfield_stats(int dtype, const void* kn, int64_t nrhs, int64_t Mp, const void* qm, const void* qS,
                            const void* y, const void* iv, const void* knn, const void* lsd, void* an, void* lam,
                            void* dm, hipStream_t s);

@@ -6,6 +6,11 @@ omega from the kernel's spectral density, b uniform on [0, 2 pi) and w standard 
 `rff_matvec` (hgp_rff_matvec) evaluates scale * W cos(...) at explicit points or on the mesh of the
 inducing grids for a few weight rows W: the (points, F) feature matrix, 16 GB at 1024^2 mesh points
 and F = 4096, is never built.  `ToeplitzInducingGP.predict_samples` is the caller.
+
+The line integral of the same draw from the origin to x, |x| int_0^1 f(a x) da, has a closed form per
+feature, |x| cos(b + T / 2) sinc(T / 2) with T = omega . x (`line_features` in torch);
+`rff_line_matvec` (hgp_rff_line_matvec) is the product with those, again without storing them, and
+`ToeplitzInducingGP.predict_line_samples` its caller.
 """
 import ctypes
 import math
@@ -101,4 +106,53 @@ def rff_matvec(omega, phase, W, x=None, xgrids=None, scale=1.0, transposed=False
                                ctypes.c_void_p(om.data_ptr()), ctypes.c_void_p(ph.data_ptr()), nfeat,
                                ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], float(scale), int(bool(transposed)),
                                float(beta), int(nsplit), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(dev)))
+    return out
+
+
+def line_features(omega, phase, x):
+    """(nobs, nfeat) line integrals |x_i| int_0^1 cos(a omega_f . x_i + phase_f) da of the features
+    along the segments from the origin to the rows of x, in torch and in the dtype of x: the closed
+    form |x| cos(phase + T / 2) sinc(T / 2), T = omega . x in radians (`torch.sinc(z)` is
+    sin(pi z) / (pi z), so z = T / 2 pi).  What `rff_line_matvec` sums without storing it."""
+    T = x.matmul(omega.t())
+    return torch.linalg.vector_norm(x, dim=1)[:, None] * torch.cos(phase + T / 2) * torch.sinc(T / TWO_PI)
+
+
+def rff_line_matvec(omega, phase, W, x, scale=1.0, transposed=False, out=None, beta=0.0, nsplit=0):
+    """scale * L W^T with L[i, f] = |x_i| int_0^1 cos(a omega_f . x_i + phase_f) da, the line integrals
+    of the features of `rff_matvec` along the segments from the origin to the rows of x (nobs, ndim),
+    without the (nobs, nfeat) matrix L (hgp_rff_line_matvec; closed form |x| cos(phase + T / 2)
+    sinc(T / 2), T = omega . x).  omega, phase, W, scale, transposed, out, beta and nsplit as
+    `rff_matvec` takes them; explicit rows only.  None for CPU tensors (the caller takes a torch
+    route, `line_features`)."""
+    if x.device.type != "cuda" or x.dtype not in (torch.float32, torch.float64):
+        return None
+    dev, dt = x.device, x.dtype
+    W = W.detach()
+    if W.dim() == 1:
+        W = W[None, :]
+    nfeat = omega.shape[0]
+    if W.dim() != 2 or W.shape[1] != nfeat or phase.numel() != nfeat:
+        raise ValueError(f"W must be (nw, nfeat) and phase (nfeat,) with nfeat = {nfeat}, got {tuple(W.shape)} "
+                         f"and {tuple(phase.shape)}")
+    Wc = W.to(device=dev, dtype=dt).contiguous()
+    om = (omega.detach().to(device=dev, dtype=torch.float64) / TWO_PI).to(dt).contiguous()
+    ph = (phase.detach().to(device=dev, dtype=torch.float64).reshape(-1) / TWO_PI).to(dt).contiguous()
+    if x.dim() != 2 or x.shape[1] != om.shape[1] or not 1 <= x.shape[1] <= 3:
+        raise ValueError(f"x must be (nobs, ndim) with ndim = {om.shape[1]} in 1..3, got {tuple(x.shape)}")
+    xc = x.detach().contiguous()
+    nobs = x.shape[0]
+    shape = (Wc.shape[0], nobs) if transposed else (nobs, Wc.shape[0])
+    if out is None:
+        if beta != 0:
+            raise ValueError("beta != 0 needs the tensor to accumulate into (out)")
+        out = torch.empty(shape, dtype=dt, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != dt or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {shape} tensor of {dt} on {dev}")
+    if nobs == 0 or Wc.shape[0] == 0:
+        return out
+    check(lib().hgp_rff_line_matvec(_lib.dtype_code(dt), x.shape[1], ctypes.c_void_p(xc.data_ptr()), nobs,
+                                    ctypes.c_void_p(om.data_ptr()), ctypes.c_void_p(ph.data_ptr()), nfeat,
+                                    ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], float(scale), int(bool(transposed)),
+                                    float(beta), int(nsplit), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(dev)))
     return out

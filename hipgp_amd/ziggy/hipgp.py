@@ -672,14 +672,22 @@ class ToeplitzInducingGP(SviGP):
     # ktilde included, up to the feature error of the prior.  Per draw: one right-hand side of the
     # batched solve, one row of the fused Kuf product and one row of the fused feature product
     # (hgp_rff_matvec), which also runs once on the whole mesh to form the right-hand side.
-    def _rff_product(self, x, omega, phase, W, scale, transposed=False, out=None, beta=0.0):
+    def _rff_product(self, x, omega, phase, W, scale, transposed=False, out=None, beta=0.0, line=False):
         """scale * cos(p omega^T + phase) W^T for weight rows W (nw, F), (npoints, nw) or transposed
         (nw, npoints), accumulated into `out` with beta = 1: the part `_kuf_product` plays for Kuf.
         The points are x, or the inducing mesh when x is None.  The fused product of `hipgp_amd.rff`
         where it applies (the features never stored), else torch over pieces of points whose
-        (piece, F) features stay under 256 MiB -- CPU stand-ins take that route."""
+        (piece, F) features stay under 256 MiB -- CPU stand-ins take that route.
+
+        line=True: the features are integrated along the segments from the origin to the rows of x
+        (`rff.rff_line_matvec`, in torch `rff.line_features`); x must be given."""
         from hipgp_amd import rff
-        if x is None:
+        if line:
+            if x is None:
+                raise TypeError("the line-integral feature product takes explicit rows x (no mesh mode)")
+            res = rff.rff_line_matvec(omega, phase, W, x, scale=scale, transposed=transposed, out=out, beta=beta)
+            pts = x
+        elif x is None:
             res = rff.rff_matvec(omega, phase, W, xgrids=self.xgrids, scale=scale, transposed=transposed, out=out,
                                  beta=beta)
             pts = self.xinduce
@@ -689,7 +697,11 @@ class ToeplitzInducingGP(SviGP):
         if res is not None:
             return res
         piece = max(1, (256 << 20) // (omega.shape[0] * pts.element_size()))
-        cols = [scale * W.matmul(torch.cos(pts[a:a + piece].matmul(omega.t()) + phase).t())
+        if line:
+            feats = lambda p: rff.line_features(omega, phase, p)
+        else:
+            feats = lambda p: torch.cos(p.matmul(omega.t()) + phase)
+        cols = [scale * W.matmul(feats(pts[a:a + piece]).t())
                 for a in range(0, pts.shape[0], piece)]
         acc = torch.cat(cols, dim=1) if cols else W.new_zeros((W.shape[0], 0))         # (nw, npoints)
         if not transposed:
@@ -765,6 +777,92 @@ class ToeplitzInducingGP(SviGP):
             out = self._kuf_product(x, alpha, False, "analytic", 10, None, None).contiguous()
             out = self._rff_product(x, omega, phase, W, scale, out=out, beta=1.0)
             return out.t().contiguous().cpu().detach()
+
+    # ---- joint draws of line integrals: the same rule with the features integrated ---------------
+    # The line integral F(x) = |x| int_0^1 f(a x) da of the prior draw above has a closed form per feature,
+    #   |x| int_0^1 cos(a T + b) da = |x| cos(b + T / 2) sinc(T / 2),   T = omega . x,
+    # and the correction term integrates to sum_j k_semi(u_j, x) alpha_j with the SAME alpha: the
+    # right-hand side is point values on the mesh, unchanged.  F at lines and f at points of one draw
+    # share v, W, xi and alpha.
+    def predict_line_samples(self, x, n, xpoint=None, nfeat=4096, eps=None, features=None, prior_w=None,
+                             nugget_eps=None, generator=None, maxiter_cg=50, Kmm=None,
+                             semi_integrated_estimator="analytic", semi_integrated_samps=10, mc_offset=None,
+                             batch_size=None):
+        """n joint draws of the LINE INTEGRALS F(x_i) = |x_i| int_0^1 f(a x_i) da of f to the rows of x,
+        (n, N) on the CPU, by the pathwise conditioning of `predict_samples`:
+        F(x) = F_prior(x) + Knm_semi(x) alpha with alpha = K^-1 (R v - f_prior(U) - sqrt(jitter) xi)
+        exactly as there (point values on the mesh), F_prior the exact line integral of the same
+        random-Fourier-feature draw (`hipgp_amd.rff.rff_line_matvec`, closed form per feature) and
+        Knm_semi the line-integral cross-covariance of `predict(integrated_obs=True)`.  Unlike
+        `predict_draws(integrated_obs=True)` the draws carry the residual ktilde.
+
+        With xpoint (Np, ndim) the result is the pair (lines (n, N), points (n, Np)): draws of f at
+        xpoint FROM THE SAME DRAWS (the same v, W, xi and alpha, one solve), equal to what
+        `predict_samples(xpoint, n, ...)` returns for the same random inputs.
+
+        One solve of n right-hand sides, the fused semi-integrated Kuf product, the fused feature
+        product on the mesh and the fused line feature product (plus the two point products with
+        xpoint); nothing of size (N, F), (M, F) or (N, M) is stored on the device route.
+
+        The feature prior is always the EXACT line integral; the cross-covariance is the caller's
+        estimator.  "analytic" (SqExp) is exact too.  With "mc-biased" (the only route for Matern;
+        `semi_integrated_samps` nodes, offset `mc_offset` or one drawn per call) the draws' mean is
+        `predict_mean`'s with that estimator, and their variance exceeds the exact one by the
+        second-order term (k~ - k)^T K^-1 (k~ - k), k~ the estimated and k the exact line-integral
+        cross-covariance: the prior and the correction no longer cancel exactly at the inducing points.
+
+        Random inputs (eps, features, prior_w, nugget_eps, generator) and the one shared feature
+        set per call as in `predict_samples`.  whitened_type='ziggy' only; SqExp and Matern kernels
+        with a scalar ell (no Gneiting, no ARD)."""
+        if self.whitened_type != 'ziggy':
+            raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        from hipgp_amd import rff
+        with torch.no_grad():
+            dev = self.xgrids[0].device
+            n = int(n)
+            x = x.to(device=dev, dtype=self.dtype)
+            if xpoint is not None:
+                xpoint = xpoint.to(device=dev, dtype=self.dtype)
+            params = self.get_kernel_params()
+            if features is None:
+                features = rff.spectral_features(self.kernel, params, len(self.xgrids), nfeat, generator=generator,
+                                                 device=dev, dtype=torch.float64)
+            omega, phase = (t.detach().to(device=dev, dtype=torch.float64) for t in features)
+            F = omega.shape[0]
+            if omega.dim() != 2 or omega.shape[1] != len(self.xgrids) or tuple(phase.shape) != (F,) or F < 1:
+                raise ValueError(f"features must be (omega (F, {len(self.xgrids)}), phase (F,)), got "
+                                 f"{tuple(omega.shape)} and {tuple(phase.shape)}")
+
+            def normal(t, shape, name):
+                if t is None:
+                    return torch.randn(shape, generator=generator, dtype=self.dtype, device=dev)
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+                return t.detach().to(device=dev, dtype=self.dtype)
+
+            v = self.variational_draws(n, eps=eps, generator=generator)
+            W = normal(prior_w, (n, F), "prior_w").contiguous()
+            xi = normal(nugget_eps, (n, self.M), "nugget_eps")
+            if x.device.type != "cuda":          # the torch route evaluates the features in the model dtype
+                omega, phase = omega.to(self.dtype), phase.to(self.dtype)
+            scale = float(torch.sqrt(2 * torch.as_tensor(params[0]).detach().double() / F))
+            if Kmm is None:
+                Kmm = self.toeplitz()
+            if hasattr(Kmm, "set_batch_shape"):
+                Kmm.set_batch_shape((n,))
+            b = Kmm._matmul_by_R(v.contiguous()).reshape(n, self.M)
+            b = b.contiguous().sub_(xi, alpha=float(np.sqrt(self.jitter_val)))
+            b = self._rff_product(None, omega, phase, W, -scale, transposed=True, out=b, beta=1.0)
+            alpha = self._solve_rows(Kmm, b, maxiter_cg, 1e-8)
+            out = self._kuf_product(x, alpha, True, semi_integrated_estimator, semi_integrated_samps, mc_offset,
+                                    batch_size).contiguous()
+            out = self._rff_product(x, omega, phase, W, scale, out=out, beta=1.0, line=True)
+            lines = out.t().contiguous().cpu().detach()
+            if xpoint is None:
+                return lines
+            pts = self._kuf_product(xpoint, alpha, False, "analytic", 10, None, None).contiguous()
+            pts = self._rff_product(xpoint, omega, phase, W, scale, out=pts, beta=1.0)
+            return lines, pts.t().contiguous().cpu().detach()
 
 
 class MeanFieldToeplitzGP(ToeplitzInducingGP):

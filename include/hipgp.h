@@ -431,6 +431,30 @@ int hgp_rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* gri
                    const void* w, int64_t nw, double scale, int transposed, double beta,
                    int64_t nsplit, void* out, void* hip_stream);
 
+/* Product with the LINE INTEGRALS of the same features, never stored: the integral of each feature
+ * along the segment from the origin to x_i, in closed form,
+ *   acc[i, s] = scale * |x_i| * sum_f w[s, f] int_0^1 cos(2 pi (a omega_f . x_i + phase_f)) da
+ *             = scale * |x_i| * sum_f w[s, f] cos(2 pi (phase_f + t / 2)) sinc(pi t),  t = omega_f . x_i,
+ *   out = beta * out + acc,
+ * with omega, phase, w, scale, transposed, beta, nsplit and out exactly as hgp_rff_matvec takes
+ * them: with the same (omega, phase, w, scale), acc is the line integral of the prior draw that
+ * entry evaluates at points.  Explicit rows x (nobs, ndim) only; there is no mesh mode.
+ * The kernel is hgp_rff_matvec's (one lane per line, wave-uniform omega / phase / w, runs of
+ * features in dtype and the runs in fp64, nsplit slices with fp64 partials, no atomics, the same
+ * bits on every call), with runs of 16 features instead of 256: the sum of one line's terms can
+ * cancel, and 256-term fp32 runs then miss the fp32 parity bound.  t / 2 is exact; fp32 takes the hardware cosine of fract(phase + t / 2) and,
+ * for |t| >= 0.25 revolutions, the hardware sine of fract(t / 2) times a reciprocal of pi t; for
+ * |t| < 0.25 sinc is its even polynomial in (pi t)^2 (five terms in fp32, nine in fp64, whose
+ * sine and cosine are libm's).  t = 0 gives sinc = 1 exactly, and a row x = 0 gives acc = 0
+ * exactly: |x_i| is applied once, where the sums are stored.
+ * Scratch as hgp_rff_matvec (nsplit > 1 only, stream-ordered).
+ * nobs = 0 or nw = 0: nothing written, 0 returned.  HGP_E_ARG (before any HIP call): null x, bad
+ * dtype / ndim, nobs / nfeat / nw / nsplit < 0, nfeat < 1 with lines present, null omega / phase /
+ * w / out.  HGP_E_HIP: the launch or the scratch allocation failed (more than 2^31 - 1 blocks). */
+int hgp_rff_line_matvec(int dtype, int ndim, const void* x, int64_t nobs, const void* omega,
+                        const void* phase, int64_t nfeat, const void* w, int64_t nw, double scale,
+                        int transposed, double beta, int64_t nsplit, void* out, void* hip_stream);
+
 /* Doubly-integrated diagonal Knn_diag by table interpolation,
  * KernelDoublyDiagInterpolator.forward (kernels.py:200-220): table = device array of 3*N
  * values in dtype (distance grid, knn, slopes: the reference's float32 table), x: (nobs,
