@@ -37,6 +37,7 @@ EXPORTS = (
     "hgp_kuf_grid_matvec", "hgp_kuf_semi_mc_matvec", "hgp_kuf_semi_sqexp_matvec",
     "hgp_kuf_grid_rmatvec", "hgp_kuf_semi_mc_rmatvec", "hgp_kuf_semi_sqexp_rmatvec",
     "hgp_plan_is_separable", "hgp_separable_detect", "hgp_rff_matvec", "hgp_rff_line_matvec",
+    "hgp_plan_band_radius", "hgp_band_radius",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -80,6 +81,8 @@ def lib():
         "hgp_plan_is_separable": (i32, [vp, ctypes.POINTER(dbl), ctypes.POINTER(dbl)]),
         "hgp_separable_detect": (i32, [i32, i64, i64, vp, dbl, ctypes.POINTER(dbl), ctypes.POINTER(dbl),
                                        ctypes.POINTER(dbl)]),
+        "hgp_plan_band_radius": (i32, [vp, pi32]),
+        "hgp_band_radius": (i32, [i64, ctypes.POINTER(dbl), pi64]),
         "hgp_pcg_rnorm2": (i32, [vp, vp]),
         "hgp_kuf_grid": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp]),
         "hgp_kuf_semi_mc": (i32, [i32, i32, dbl, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, i32, vp, vp, vp]),

@@ -6,10 +6,12 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hipgp.h"
 #include "hgp_internal.hpp"
+#include "hgp_band.hpp"
 #include "hgp_sep.hpp"
 #include "hgp_sep_host.hpp"
 
@@ -183,6 +185,14 @@ struct hgp_plan {
   double sep_sigma = 0, sep_k00 = 0, sep_resid = 0;
   DevBuf sepS0, sepS1;                    // the two real 1-D spectra (L_K[0], L_K[1] values)
   DevBuf sepW;                            // set-up: 4 words + m0 + m1 + 2 doubles (sep_detect_dev)
+  // Banded product form (hgp_band.hpp): an fp32 product-form plan whose two factor
+  // columns vanish in fp32 beyond band_r[a] <= HGP_BAND_RMAX taps (band_radius) runs the two passes
+  // as banded matrix products on the matrix cores, with no transform.  HGP_BANDED=0 (read by every
+  // set_column): never.  band_r = -1 where the plan is not in product form.
+  bool band_allowed = true;
+  bool band = false;
+  int64_t band_r[2] = {-1, -1};
+  DevBuf bandT;                           // 2 x BAND_TAPS fp32 taps (axis 0, axis 1), zero beyond the radii
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   // hipGraph of a repeated hgp_toeplitz_apply (same op, buffers, RHS count, workspaces, stream):
@@ -196,12 +206,15 @@ struct hgp_plan {
     // every plan-owned buffer an op's launches address (workspaces, the full-grid route's
     // buffers, the spectra): a reallocation of any of them -- e.g. R^T on a grid_k plan growing
     // gridA / gridB past K's size -- must invalidate a captured graph
-    static constexpr int NB = 12;
+    static constexpr int NB = 13;
     const void* buf[NB] = {};
     bool sep = false;                     // the product-form path (hgp_plan::separable) was on
+    bool band = false;                    // ... as banded products (hgp_plan::band), of these radii
+    int64_t br0 = 0, br1 = 0;
     double sigma = 0;                     // its jitter: a by-value kernel argument of the captured launches
     bool operator==(const ApplyKey& o) const {
-      if (!(op == o.op && x == o.x && y == o.y && nrhs == o.nrhs && stream == o.stream && sep == o.sep && sigma == o.sigma)) return false;
+      if (!(op == o.op && x == o.x && y == o.y && nrhs == o.nrhs && stream == o.stream && sep == o.sep && sigma == o.sigma &&
+            band == o.band && br0 == o.br0 && br1 == o.br1)) return false;
       for (int i = 0; i < NB; ++i)
         if (buf[i] != o.buf[i]) return false;
       return true;
@@ -209,10 +222,13 @@ struct hgp_plan {
   };
   void key_buffers(ApplyKey& k) const {
     const DevBuf* b[ApplyKey::NB] = {&ws1, &ws2, &gridA, &gridB, &specK, &specI, &specR, &specRg, &specKg,
-                                     &specR2, &sepS0, &sepS1};
+                                     &specR2, &sepS0, &sepS1, &bandT};
     for (int i = 0; i < ApplyKey::NB; ++i) k.buf[i] = b[i]->ptr;
     k.sep = separable;
     k.sigma = separable ? sep_sigma : 0;
+    k.band = band;
+    k.br0 = band ? band_r[0] : 0;
+    k.br1 = band ? band_r[1] : 0;
   }
   ApplyKey last_apply, graph_key;
   hipGraphExec_t graph_exec = nullptr;
@@ -234,7 +250,7 @@ struct hgp_plan {
     }
     DevBuf* bufs[] = {&specK, &specI, &specR, &specR2, &specRg, &specKg, &gridA, &gridB, &Dm3, &nclamp, &ws1, &ws2, &set1, &set2, &setM1, &setM2, &setC,
                       &r, &z, &p, &Ap, &part_op, &part_u, &part_f, &scal, &flags, &bT, &xT, &st_part, &st_kn, &st_lam,
-                      &sepS0, &sepS1, &sepW};
+                      &sepS0, &sepS1, &sepW, &bandT};
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 3; ++i) {
       if (side[i]) (void)hipStreamDestroy(side[i]);
@@ -509,6 +525,18 @@ int sep_finish(hgp_plan* P) {
     HIP_TRY(hipStreamSynchronize(P->stream));   // sT is a temporary
   }
   P->separable = true;
+  // the factors' tap radii; short ones in fp32 take the banded passes (hgp_band.hpp)
+  P->band_r[0] = band_radius(t, m0);
+  P->band_r[1] = band_radius(t + m0, m1);
+  if (std::is_same<T, float>::value && P->band_allowed && P->band_r[0] <= HGP_BAND_RMAX && P->band_r[1] <= HGP_BAND_RMAX) {
+    std::vector<float> taps(2 * BAND_TAPS, 0.f);
+    for (int64_t j = 0; j <= P->band_r[0]; ++j) taps[(size_t)j] = (float)t[j];
+    for (int64_t j = 0; j <= P->band_r[1]; ++j) taps[(size_t)(BAND_TAPS + j)] = (float)t[m0 + j];
+    HGP_TRY(P->bandT.ensure(taps.size() * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(P->bandT.ptr, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, P->stream));
+    HIP_TRY(hipStreamSynchronize(P->stream));   // taps is a temporary
+    P->band = true;
+  }
   return 0;
 }
 
@@ -568,6 +596,54 @@ int run_sep(hgp_plan* P, const void* x, void* y, int64_t nrhs, const int* done) 
   return 0;
 }
 
+// the same product as two banded matrix products (hgp_band.hpp): V = X S1 into the plain real
+// workspace V[q][i0][i1], then y = S0^T V + sigma x.  Chunks, streams and workspace as run_sep.
+int run_band(hgp_plan* P, const void* x, void* y, int64_t nrhs, const int* done) {
+  const int64_t m0 = P->m[0], m1 = P->m[1];
+  const int64_t per = P->M * (int64_t)sizeof(float);
+  const int NS = (int)std::min<int64_t>(std::max(1, P->nstreams), nrhs);
+  int64_t Qc = std::max<int64_t>(1, std::min<int64_t>((nrhs + NS - 1) / NS, P->ws_budget / (per * NS)));
+  // chunks whose intermediate stays in the Infinity Cache between the two passes, as run_sep's
+  if (!P->ws_explicit && per * 8 <= ((int64_t)72 << 20)) Qc = std::min<int64_t>(Qc, 8);
+  HGP_TRY(P->ws1.ensure((size_t)(per * Qc * NS)));
+  hipStream_t streams[4] = {P->stream, nullptr, nullptr, nullptr};
+  if (NS > 1) {
+    HGP_TRY(ensure_side_streams(P, NS));
+    HIP_TRY(hipEventRecord(P->ev_fork, P->stream));
+    for (int i = 1; i < NS; ++i) {
+      streams[i] = P->side[i - 1];
+      HIP_TRY(hipStreamWaitEvent(streams[i], P->ev_fork, 0));
+    }
+  }
+  const float* xin = reinterpret_cast<const float*>(x);
+  float* yout = reinterpret_cast<float*>(y);
+  const float* taps = reinterpret_cast<const float*>(P->bandT.ptr);
+  const int64_t nch = (nrhs + Qc - 1) / Qc;
+  for (int64_t chunk = 0; chunk < nch; ++chunk) {
+    const int64_t q0 = chunk * Qc;
+    const int qn = (int)(std::min(nrhs, q0 + Qc) - q0);
+    const int slot = (int)(chunk % NS);
+    hipStream_t st = streams[slot];
+    float* V = reinterpret_cast<float*>(P->ws1.ptr) + (int64_t)slot * Qc * P->M;
+    BandDesc A;
+    std::memset(&A, 0, sizeof(A));
+    A.in = xin + q0 * P->M; A.out = V; A.taps = taps + BAND_TAPS; A.m0 = (int)m0; A.m1 = (int)m1;
+    A.r = (int)((P->band_r[1] + 1) / 2 * 2); A.Q = qn; A.done = done;
+    BandDesc B = A;
+    B.in = V; B.out = yout + q0 * P->M; B.taps = taps; B.r = (int)((P->band_r[0] + 1) / 2 * 2);
+    B.add = P->sep_sigma != 0 ? xin + q0 * P->M : nullptr; B.sigma = (float)P->sep_sigma;
+    for (int ax = 1; ax >= 0; --ax) {
+      hipError_t e = launch_band(ax, ax == 1 ? A : B, st);
+      if (e != hipSuccess) return fail(HGP_E_HIP, std::string("banded pass launch: ") + hipGetErrorString(e));
+    }
+  }
+  for (int i = 1; i < NS; ++i) {
+    HIP_TRY(hipEventRecord(P->ev_join[i - 1], streams[i]));
+    HIP_TRY(hipStreamWaitEvent(P->stream, P->ev_join[i - 1], 0));
+  }
+  return 0;
+}
+
 template <typename T>
 int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void* dotv, void* partial,
            const int* done, int only_pass = -1, void* spart = nullptr, const RowEpi* epi = nullptr,
@@ -576,7 +652,7 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
   // and so does the pass split (hgp_toeplitz_apply_pass times the general sequence's three passes)
   if (op == HGP_OP_K && P->separable && only_pass < 0 && dotv == nullptr && partial == nullptr && spart == nullptr &&
       epi == nullptr && mid == nullptr && pair == nullptr && stats == nullptr)
-    return run_sep<T>(P, x, y, nrhs, done);
+    return P->band ? run_band(P, x, y, nrhs, done) : run_sep<T>(P, x, y, nrhs, done);
   if (grid_route(P, op)) {
     if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "internal: HGP_OP_RSQ has no full-grid route");
     if (spart != nullptr || epi != nullptr || mid != nullptr || only_pass >= 0 || stats != nullptr)
@@ -1324,6 +1400,10 @@ int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_mi
   P->sep_pending = sep_try;
   P->separable = false;
   P->sep_sigma = P->sep_k00 = P->sep_resid = 0;
+  const char* bp = std::getenv("HGP_BANDED");
+  P->band_allowed = !(bp && std::atoi(bp) == 0);
+  P->band = false;
+  P->band_r[0] = P->band_r[1] = -1;
   if (sep_try) {
     HGP_TRY(P->sepW.ensure((size_t)(4 + P->m[0] + P->m[1] + 2) * sizeof(double)));
     unsigned long long* w = reinterpret_cast<unsigned long long*>(P->sepW.ptr);
@@ -2197,6 +2277,20 @@ int hgp_plan_is_separable(hgp_plan* plan, double* sigma, double* resid) {
   if (sigma) *sigma = plan->sep_sigma;
   if (resid) *resid = plan->sep_resid;
   return plan->separable ? 1 : 0;
+}
+
+int hgp_plan_band_radius(hgp_plan* plan, int r[2]) {
+  HGP_TRY(check_plan(plan));
+  if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  HGP_TRY(sep_resolve(plan));
+  if (r) { r[0] = (int)plan->band_r[0]; r[1] = (int)plan->band_r[1]; }
+  return plan->band ? 1 : 0;
+}
+
+int hgp_band_radius(int64_t m, const double* t, int64_t* r) {
+  if (t == nullptr || r == nullptr || m < 1) return fail(HGP_E_ARG, "hgp_band_radius: bad argument");
+  *r = band_radius(t, m);
+  return 0;
 }
 
 int hgp_separable_detect(int dtype, int64_t m0, int64_t m1, const void* column, double jitter, double* out4,

@@ -80,6 +80,23 @@ inline SepFactors sep_detect(const double* c, int64_t m0, int64_t m1, double eps
   return f;
 }
 
+// Tap radius of a factor column t (m values) for the banded passes (hgp_band.hpp): the
+// smallest r with 2 sum_{j > r} |t[j]| <= 2^-25 (|t[0]| + 2 sum_{j >= 1} |t[j]|), i.e. the taps
+// beyond r hold at most half an fp32 rounding unit of the Toeplitz matrix' row sum.  Dropping them
+// on both axes changes K x by at most 2^-24 ||t0||_1 ||t1||_1 max |x|.  Sums run from the small
+// end; a NaN keeps every tap (r = m - 1).
+inline int64_t band_radius(const double* t, int64_t m) {
+  if (m < 1) return 0;
+  double total = 0;
+  for (int64_t j = m - 1; j >= 1; --j) total += 2.0 * std::fabs(t[j]);
+  total += std::fabs(t[0]);
+  const double bound = 2.98023223876953125e-08 * total;            // 2^-25
+  double tail = 0;
+  int64_t r = m - 1;
+  while (r > 0 && 2.0 * (tail + std::fabs(t[r])) <= bound) { tail += std::fabs(t[r]); --r; }
+  return r;
+}
+
 // in-place radix-2 FFT (forward sign), n a power of two
 inline void sep_fft(std::vector<std::complex<double>>& a) {
   const size_t n = a.size();

@@ -166,6 +166,20 @@ int hgp_plan_is_separable(hgp_plan* plan, double* sigma, double* resid);
 int hgp_separable_detect(int dtype, int64_t m0, int64_t m1, const void* column, double jitter, double* out4,
                          double* t0, double* t1);
 
+/* Banded product form.  A product-form fp32 plan whose factor columns t0, t1 vanish in fp32 beyond
+ * a few taps runs the two passes as banded matrix products on the matrix cores, with no transform.
+ * The tap radius of a factor t of m values is the smallest r with
+ *   2 sum_{j > r} |t[j]| <= 2^-25 (|t[0]| + 2 sum_{j >= 1} |t[j]|);
+ * dropping the taps beyond it changes K x by at most 2^-24 ||t0||_1 ||t1||_1 max |x|.  The banded
+ * passes run where both radii are at most 32 (the library's HGP_BAND_RMAX) and the environment
+ * variable HGP_BANDED, read by every hgp_plan_set_column, is not 0.
+ * hgp_plan_band_radius: 1 if the last column runs the banded passes, else 0 (a negative HGP_E* code
+ * on error); r (optional) receives the two radii, -1 where the plan is not in product form.  It
+ * settles the product-form decision as hgp_plan_is_separable does.
+ * hgp_band_radius applies the rule to a HOST column t of m doubles (no device). */
+int hgp_plan_band_radius(hgp_plan* plan, int r[2]);
+int hgp_band_radius(int64_t m, const double* t, int64_t* r);
+
 /* Stepwise PCG for the callback form of conj_grad/conj_grad2 (cg.py:77-78): begin() sets
  * x0 = 0, r = b, z = P r, p = z; step() runs one iteration and, if `converged` != NULL,
  * reports (synchronising) whether the break test fired on it.  x is updated in place in the
