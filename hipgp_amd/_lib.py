@@ -37,7 +37,7 @@ EXPORTS = (
     "hgp_kuf_grid_matvec", "hgp_kuf_semi_mc_matvec", "hgp_kuf_semi_sqexp_matvec",
     "hgp_kuf_grid_rmatvec", "hgp_kuf_semi_mc_rmatvec", "hgp_kuf_semi_sqexp_rmatvec",
     "hgp_plan_is_separable", "hgp_separable_detect", "hgp_rff_matvec", "hgp_rff_line_matvec",
-    "hgp_plan_band_radius", "hgp_band_radius",
+    "hgp_plan_band_radius", "hgp_band_radius", "hgp_plan_band_fused", "hgp_band_fused_tile",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -83,6 +83,8 @@ def lib():
                                        ctypes.POINTER(dbl)]),
         "hgp_plan_band_radius": (i32, [vp, pi32]),
         "hgp_band_radius": (i32, [i64, ctypes.POINTER(dbl), pi64]),
+        "hgp_plan_band_fused": (i32, [vp]),
+        "hgp_band_fused_tile": (i32, [pi32]),
         "hgp_pcg_rnorm2": (i32, [vp, vp]),
         "hgp_kuf_grid": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, vp, vp]),
         "hgp_kuf_semi_mc": (i32, [i32, i32, dbl, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, i32, vp, vp, vp]),

@@ -12,6 +12,7 @@
 #include "../../include/hipgp.h"
 #include "hgp_internal.hpp"
 #include "hgp_band.hpp"
+#include "hgp_band_fused.hpp"
 #include "hgp_sep.hpp"
 #include "hgp_sep_host.hpp"
 
@@ -191,6 +192,10 @@ struct hgp_plan {
   // set_column): never.  band_r = -1 where the plan is not in product form.
   bool band_allowed = true;
   bool band = false;
+  // ... and those in one kernel with V in LDS (hgp_band_fused.hpp) unless
+  // HGP_BAND_FUSED=0 (read by every set_column), which keeps run_band's two passes
+  bool band_fused_allowed = true;
+  bool band_fused = false;
   int64_t band_r[2] = {-1, -1};
   DevBuf bandT;                           // 2 x BAND_TAPS fp32 taps (axis 0, axis 1), zero beyond the radii
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
@@ -210,11 +215,12 @@ struct hgp_plan {
     const void* buf[NB] = {};
     bool sep = false;                     // the product-form path (hgp_plan::separable) was on
     bool band = false;                    // ... as banded products (hgp_plan::band), of these radii
+    bool bfused = false;                  // ... in the fused kernel (hgp_plan::band_fused)
     int64_t br0 = 0, br1 = 0;
     double sigma = 0;                     // its jitter: a by-value kernel argument of the captured launches
     bool operator==(const ApplyKey& o) const {
       if (!(op == o.op && x == o.x && y == o.y && nrhs == o.nrhs && stream == o.stream && sep == o.sep && sigma == o.sigma &&
-            band == o.band && br0 == o.br0 && br1 == o.br1)) return false;
+            band == o.band && bfused == o.bfused && br0 == o.br0 && br1 == o.br1)) return false;
       for (int i = 0; i < NB; ++i)
         if (buf[i] != o.buf[i]) return false;
       return true;
@@ -227,6 +233,7 @@ struct hgp_plan {
     k.sep = separable;
     k.sigma = separable ? sep_sigma : 0;
     k.band = band;
+    k.bfused = band && band_fused;
     k.br0 = band ? band_r[0] : 0;
     k.br1 = band ? band_r[1] : 0;
   }
@@ -536,6 +543,7 @@ int sep_finish(hgp_plan* P) {
     HIP_TRY(hipMemcpyAsync(P->bandT.ptr, taps.data(), taps.size() * sizeof(float), hipMemcpyHostToDevice, P->stream));
     HIP_TRY(hipStreamSynchronize(P->stream));   // taps is a temporary
     P->band = true;
+    P->band_fused = P->band_fused_allowed;
   }
   return 0;
 }
@@ -644,6 +652,23 @@ int run_band(hgp_plan* P, const void* x, void* y, int64_t nrhs, const int* done)
   return 0;
 }
 
+// the two banded products in one kernel (hgp_band_fused.hpp): one launch over all the right-hand
+// sides on the plan's stream, no workspace, no side streams
+int run_band_fused(hgp_plan* P, const void* x, void* y, int64_t nrhs, const int* done) {
+  if (nrhs > 0x7fffffff) return fail(HGP_E_ARG, "banded product: too many right-hand sides");
+  const float* taps = reinterpret_cast<const float*>(P->bandT.ptr);
+  BandFusedDesc F;
+  std::memset(&F, 0, sizeof(F));
+  F.in = reinterpret_cast<const float*>(x); F.out = reinterpret_cast<float*>(y);
+  F.add = P->sep_sigma != 0 ? 1 : 0; F.sigma = (float)P->sep_sigma;
+  F.taps0 = taps; F.taps1 = taps + BAND_TAPS; F.m0 = (int)P->m[0]; F.m1 = (int)P->m[1];
+  F.r0 = (int)((P->band_r[0] + 1) / 2 * 2); F.r1 = (int)((P->band_r[1] + 1) / 2 * 2);
+  F.Q = (int)nrhs; F.done = done;
+  hipError_t e = launch_band_fused(F, P->stream);
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("fused banded product launch: ") + hipGetErrorString(e));
+  return 0;
+}
+
 template <typename T>
 int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void* dotv, void* partial,
            const int* done, int only_pass = -1, void* spart = nullptr, const RowEpi* epi = nullptr,
@@ -652,7 +677,8 @@ int run_op(hgp_plan* P, int op, const void* x, void* y, int64_t nrhs, const void
   // and so does the pass split (hgp_toeplitz_apply_pass times the general sequence's three passes)
   if (op == HGP_OP_K && P->separable && only_pass < 0 && dotv == nullptr && partial == nullptr && spart == nullptr &&
       epi == nullptr && mid == nullptr && pair == nullptr && stats == nullptr)
-    return P->band ? run_band(P, x, y, nrhs, done) : run_sep<T>(P, x, y, nrhs, done);
+    return P->band ? (P->band_fused ? run_band_fused(P, x, y, nrhs, done) : run_band(P, x, y, nrhs, done))
+                   : run_sep<T>(P, x, y, nrhs, done);
   if (grid_route(P, op)) {
     if (op == HGP_OP_RSQ) return fail(HGP_E_UNSUPPORTED, "internal: HGP_OP_RSQ has no full-grid route");
     if (spart != nullptr || epi != nullptr || mid != nullptr || only_pass >= 0 || stats != nullptr)
@@ -1404,6 +1430,9 @@ int set_column_t(hgp_plan* P, const void* column, double jitter, double clamp_mi
   P->band_allowed = !(bp && std::atoi(bp) == 0);
   P->band = false;
   P->band_r[0] = P->band_r[1] = -1;
+  const char* bf = std::getenv("HGP_BAND_FUSED");
+  P->band_fused_allowed = !(bf && std::atoi(bf) == 0);
+  P->band_fused = false;
   if (sep_try) {
     HGP_TRY(P->sepW.ensure((size_t)(4 + P->m[0] + P->m[1] + 2) * sizeof(double)));
     unsigned long long* w = reinterpret_cast<unsigned long long*>(P->sepW.ptr);
@@ -2285,6 +2314,19 @@ int hgp_plan_band_radius(hgp_plan* plan, int r[2]) {
   HGP_TRY(sep_resolve(plan));
   if (r) { r[0] = (int)plan->band_r[0]; r[1] = (int)plan->band_r[1]; }
   return plan->band ? 1 : 0;
+}
+
+int hgp_plan_band_fused(hgp_plan* plan) {
+  HGP_TRY(check_plan(plan));
+  if (!plan->have_spec) return fail(HGP_E_STATE, "hgp_plan_set_column has not been called");
+  HGP_TRY(sep_resolve(plan));
+  return plan->band && plan->band_fused ? 1 : 0;
+}
+
+int hgp_band_fused_tile(int tile[2]) {
+  if (tile == nullptr) return fail(HGP_E_ARG, "hgp_band_fused_tile: bad argument");
+  band_fused_tile(tile);
+  return 0;
 }
 
 int hgp_band_radius(int64_t m, const double* t, int64_t* r) {

@@ -180,6 +180,14 @@ int hgp_separable_detect(int dtype, int64_t m0, int64_t m1, const void* column, 
 int hgp_plan_band_radius(hgp_plan* plan, int r[2]);
 int hgp_band_radius(int64_t m, const double* t, int64_t* r);
 
+/* The banded passes run as ONE kernel that keeps the intermediate V = X S1 in LDS, bit
+ * for bit the two-pass result, unless HGP_BAND_FUSED=0 was set when hgp_plan_set_column was called.
+ * hgp_plan_band_fused: 1 if the last column's K matvec takes the fused kernel, else 0 (a negative
+ * HGP_E* code on error).  hgp_band_fused_tile: {rows of a block's segment, columns of its strip} of
+ * the built kernel, both multiples of 16 (no device). */
+int hgp_plan_band_fused(hgp_plan* plan);
+int hgp_band_fused_tile(int tile[2]);
+
 /* Stepwise PCG for the callback form of conj_grad/conj_grad2 (cg.py:77-78): begin() sets
  * x0 = 0, r = b, z = P r, p = z; step() runs one iteration and, if `converged` != NULL,
  * reports (synchronising) whether the break test fired on it.  x is updated in place in the

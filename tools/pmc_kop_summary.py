@@ -15,7 +15,7 @@ import sys
 
 root, out = sys.argv[1], sys.argv[2]
 nops = int(sys.argv[3]) if len(sys.argv) > 3 else 13
-OP_KERNELS = ("k_row_fwd_t", "k_row_inv_t", "k_pass<float", "k_sep_pass", "k_band_row", "k_band_col")
+OP_KERNELS = ("k_row_fwd_t", "k_row_inv_t", "k_pass<float", "k_sep_pass", "k_band_row", "k_band_col", "k_band_fused")
 vals = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(os.path.join(root, "**", "*counter_collection.csv"), recursive=True):
     with open(f) as fh:
