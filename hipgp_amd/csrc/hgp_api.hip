@@ -2693,6 +2693,48 @@ int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void
   return 0;
 }
 
+// the windowed products: the dense entries' checks, and rho; all before any HIP call
+static int check_win_rho(double rho) {
+  if (!(rho >= 0) || !std::isfinite(rho)) return fail(HGP_E_ARG, "rho must be finite and >= 0");
+  return 0;
+}
+
+int hgp_kuf_grid_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                            int64_t nobs, double sig2, double ell, double rho, const void* w, int64_t nw, void* out,
+                            void* hip_stream) {
+  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
+  HGP_TRY(check_win_rho(rho));
+  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
+  if (c != 0) return c > 0 ? 0 : c;
+  hipError_t e = kuf_matvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell, rho, w, nw, out,
+                                reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_matvec_win: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                             int64_t nobs, double sig2, double ell, double rho, const void* c, int64_t nc,
+                             const int64_t* order, const int64_t* bin_start, void* out, void* hip_stream) {
+  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
+  HGP_TRY(check_win_rho(rho));
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  if (nobs > 0 && (order == nullptr || bin_start == nullptr)) return fail(HGP_E_ARG, "null order / bin_start");
+  hipError_t e = kuf_rmatvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell, rho, c, nc, order, bin_start, out,
+                                 reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_rmatvec_win: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_win_bins(int ndim, const int64_t* m, int64_t* tile_out, int64_t* nbins_out) {
+  if (ndim < 1 || ndim > 3 || m == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m non-null");
+  if (tile_out == nullptr || nbins_out == nullptr) return fail(HGP_E_ARG, "null tile_out / nbins_out");
+  for (int a = 0; a < ndim; ++a)
+    if (m[a] < 1) return fail(HGP_E_ARG, "grid sizes must be >= 1");
+  kuf_win_geometry(ndim, m, tile_out, nbins_out);
+  return 0;
+}
+
 int hgp_rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
                    const void* omega, const void* phase, int64_t nfeat, const void* w, int64_t nw, double scale,
                    int transposed, double beta, int64_t nsplit, void* out, void* hip_stream) {

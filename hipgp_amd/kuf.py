@@ -18,6 +18,10 @@ mean and draws at many points need once K^-1 R v is solved (`ToeplitzInducingGP.
 Their transposes, `kuf_grid_rmatvec` / `kuf_semi_mc_rmatvec` / `kuf_semi_sqexp_rmatvec`
 (hgp_kuf_*_rmatvec): C @ Knm for a few coefficient rows C, the other half of the matrix-free
 operator K + Knm^T diag(iv) Knm behind `ToeplitzInducingGP.fit_mean`.
+
+The point-observation pair of those also over a window, for kernels far shorter than the grid:
+`support_radius` (the truncation rule), `WindowPlan`, `kuf_grid_matvec_win` / `kuf_grid_rmatvec_win`
+(hgp_kuf_grid_matvec_win / hgp_kuf_grid_rmatvec_win), within tol * sig2 * sum |w| of the dense ones.
 """
 import ctypes
 
@@ -289,6 +293,167 @@ def kuf_semi_sqexp_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
                                            ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el,
                                            ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
                                            ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+    return out
+
+
+# ---- the same two products over a window: kernels far shorter than the grid ----------------------
+# A point only sees the nodes within the kernel's reach.  `support_radius` is the truncation rule,
+# `WindowPlan` holds what the two products share for one set of points, `kuf_grid_matvec_win` /
+# `kuf_grid_rmatvec_win` are the products (hgp_kuf_grid_matvec_win / hgp_kuf_grid_rmatvec_win).  Per
+# output the windowed product is within tol * sig2 * sum |w| (or sum |c|) of the dense one.
+
+def _kern_unit64(kind, r, el):
+    """k(r) / sig2 in fp64 by the formulas of the device's `kern_eval`."""
+    import math
+    if kind == _lib.KERN_SQEXP:
+        dv = r / el
+        return math.exp(-(dv * dv) / 2)
+    if kind == _lib.KERN_MATERN12:
+        return math.exp(-r / el)
+    if kind == _lib.KERN_MATERN32:
+        dp = 1.7320508075688772935 * r / el
+        return (1 + dp) * math.exp(-dp)
+    dp = 2.2360679774997896964 * r / el
+    return (1 + dp + (5. / 3.) * (r * r) / (el * el)) * math.exp(-dp)
+
+
+def support_radius(kernel, params, tol):
+    """The smallest distance rho (a float, fp64) with k(r) <= tol * sig2 for every r >= rho, or
+    None where no rule applies: Gneiting or a kernel without a fused forward, a vector `ell`, `tol`
+    outside (0, 1).  SqExp in closed form, ell * sqrt(2 ln(1 / tol)) (moved up by at most a few ulps
+    so that the fp64 formula itself is <= tol there); Matern 1/2, 3/2, 5/2, all decreasing in r, by
+    bisection on the fp64 formula."""
+    import math
+    kind = kernel_kind(kernel)
+    if kind is None or tol is None:
+        return None
+    tol = float(tol)
+    if not (0. < tol < 1.):
+        return None
+    sig2, ell = params
+    s2, el = _scalar(sig2), _scalar(ell)
+    if s2 is None or el is None or not (el > 0) or not math.isfinite(el):
+        return None
+    if kind == _lib.KERN_SQEXP:
+        rho = el * math.sqrt(2 * math.log(1 / tol))
+        for _ in range(4):
+            if _kern_unit64(kind, rho, el) <= tol:
+                break
+            rho = math.nextafter(rho, math.inf)
+        return rho
+    lo, hi = 0., el
+    while _kern_unit64(kind, hi, el) > tol:
+        lo, hi = hi, 2 * hi
+    for _ in range(200):                  # k(lo) > tol >= k(hi) throughout
+        mid = .5 * (lo + hi)
+        if not (lo < mid < hi):
+            break
+        if _kern_unit64(kind, mid, el) <= tol:
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def win_bins(dims):
+    """(tile, nbins) per axis as hgp_kuf_grid_rmatvec_win assumes them (hgp_kuf_win_bins): along
+    axis a a tile has tile[a] mesh points and a bin tile[a] cells; nbins[a] = m[a] // tile[a] + 1."""
+    nd = len(dims)
+    m = (ctypes.c_int64 * nd)(*[int(v) for v in dims])
+    tile, nbins = (ctypes.c_int64 * 3)(), (ctypes.c_int64 * 3)()
+    check(lib().hgp_kuf_win_bins(nd, m, tile, nbins))
+    return list(tile)[:nd], list(nbins)[:nd]
+
+
+class WindowPlan:
+    """What the windowed products share for one set of points x against one grid: the radius rho
+    (`support_radius(kernel, params, tol)`, or the given `rho`), the contiguous grids and x, and
+    the observations sorted by bin (`order`, `bin_start`; built on the first transposed product).
+    Build it once and use it for any number of products; x, the grids and the kernel parameters
+    are read here and must not change while the plan is in use.
+
+    Pair (n, j) is in the window iff |x[n, a] - g_a[j_a]| <= rho on every axis a, evaluated in
+    x's dtype with rho rounded once to that dtype.  The constructor raises ValueError where the
+    windowed products do not apply; `WindowPlan.make` returns None there instead."""
+
+    def __init__(self, kernel, xgrids, x, params, tol, rho=None):
+        a = _grid_call_args(kernel, xgrids, x, params)
+        if rho is None:
+            rho = support_radius(kernel, params, tol)
+        if a is None or rho is None or not (float(rho) >= 0) or float(rho) == float("inf"):
+            raise ValueError("the windowed Kuf products do not apply: they take SqExp / Matern(1/2, 3/2, 5/2) with a "
+                             "scalar ell, a tolerance in (0, 1), device points (nobs, D <= 3) in fp32 / fp64 and no "
+                             "graph to x, sig2 or ell")
+        self.kind, self.sig2, self.ell, self.grids, self.x, self.M = a
+        self.rho, self.tol = float(rho), tol
+        self.dims = [g.numel() for g in self.grids]
+        self._bins = None
+
+    @classmethod
+    def make(cls, kernel, xgrids, x, params, tol, rho=None):
+        """The plan, or None where `support_radius` or the fused grid kernels decline."""
+        try:
+            return cls(kernel, xgrids, x, params, tol, rho=rho)
+        except ValueError:
+            return None
+
+    @property
+    def nobs(self):
+        return self.x.shape[0]
+
+    def bins(self):
+        """(order, bin_start): the observations sorted stably by bin, and the bins' offsets in that
+        list (total bins + 1), both int64 on the device.  The bin of x on axis a is (number of
+        nodes <= x_a) // tile[a]; bins are numbered in C order over the axes."""
+        if self._bins is None:
+            tile, nbins = win_bins(self.dims)
+            b = torch.zeros(self.nobs, dtype=torch.int64, device=self.x.device)
+            total = 1
+            for a, g in enumerate(self.grids):
+                cell = torch.searchsorted(g, self.x[:, a].contiguous(), right=True).clamp_(0, g.numel())
+                b = b * nbins[a] + torch.div(cell, tile[a], rounding_mode="floor")
+                total *= nbins[a]
+            order = torch.sort(b, stable=True).indices.contiguous()
+            start = torch.zeros(total + 1, dtype=torch.int64, device=self.x.device)
+            start[1:] = torch.cumsum(torch.bincount(b, minlength=total), 0)
+            self._bins = (order, start)
+        return self._bins
+
+
+def kuf_grid_matvec_win(plan, W):
+    """The windowed kuf_grid(...) @ W^T, (nobs, nw), for the plan's points (hgp_kuf_grid_matvec_win):
+    W is (nw, M) or (M,).  Within plan.tol * sig2 * sum_j |W[s, j]| of `kuf_grid_matvec` per output;
+    a point with an empty window gives exact zeros.  None where W carries a graph."""
+    x = plan.x
+    Wc = _matvec_weights(W, x, plan.M)
+    if Wc is None:
+        return None
+    out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
+    m, ptrs = _grid_ptrs(plan.grids)
+    check(lib().hgp_kuf_grid_matvec_win(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
+                                        ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho,
+                                        ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], ctypes.c_void_p(out.data_ptr()),
+                                        _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_grid_rmatvec_win(plan, C):
+    """The windowed C @ kuf_grid(...), (nc, M), for the plan's points (hgp_kuf_grid_rmatvec_win): C is
+    (nc, nobs) or (nobs,).  The exact transpose of `kuf_grid_matvec_win` on the same plan (the same
+    pairs, the same element values); within plan.tol * sig2 * sum_n |C[s, n]| of `kuf_grid_rmatvec`
+    per output.  No observations: zeros.  None where C carries a graph."""
+    x = plan.x
+    Cc = _rmatvec_coefs(C, x)
+    if Cc is None:
+        return None
+    out = torch.empty((Cc.shape[0], plan.M), dtype=x.dtype, device=x.device)
+    order, start = plan.bins() if x.shape[0] > 0 else (None, None)
+    m, ptrs = _grid_ptrs(plan.grids)
+    ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+    check(lib().hgp_kuf_grid_rmatvec_win(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
+                                         ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho,
+                                         ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], ptr(order), ptr(start),
+                                         ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
     return out
 
 

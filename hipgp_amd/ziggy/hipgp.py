@@ -27,6 +27,7 @@ Not built (OUT of the hot path): the full-rank variational family
 (`FullRankToeplitzGP`, `hipgp.py:693-797`: a dense M' x M' covariance, 70 TB at C2).
 """
 import collections
+import contextlib
 import os
 
 import numpy as np
@@ -448,6 +449,39 @@ class ToeplitzInducingGP(SviGP):
             return Kmm.inv_matmul_(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
         return Kmm.inv_matmul(b, do_precond=True, maxiter=maxiter_cg, tol=tol)
 
+    # ---- the windowed Kuf products: a kernel far shorter than the grid ----------------------------
+    # With a support tolerance (the `support_tol` argument where a method has one, else the
+    # attribute `kuf_support_tol`, else env HGP_KUF_SUPPORT_TOL) `_kuf_product` / `_kuf_rproduct`
+    # take `kuf.kuf_grid_matvec_win` / `kuf.kuf_grid_rmatvec_win` for point observations, through
+    # one `kuf.WindowPlan` per (x, dtype) kept for the length of the public call.  With none set,
+    # `self._win` stays None and nothing below changes.
+    @contextlib.contextmanager
+    def _windowed(self, support_tol, integrated_obs):
+        tol = self._kuf_support_tol(support_tol)
+        if tol is not None and integrated_obs:
+            raise NotImplementedError("a support tolerance with integrated_obs=True: the window of a line integral is "
+                                      "a tube around the segment and is not built; unset support_tol / "
+                                      "kuf_support_tol / HGP_KUF_SUPPORT_TOL for line-integral observations")
+        prev = getattr(self, "_win", None)
+        self._win = None if tol is None else {"tol": tol, "plans": {}}
+        try:
+            yield
+        finally:
+            self._win = prev
+
+    def _window_plan(self, x, params):
+        """The call's `kuf.WindowPlan` for the points x (one per x and dtype), or None: no tolerance
+        is set, or the plan declines (the dense route then runs as before)."""
+        win = getattr(self, "_win", None)
+        if win is None:
+            return None
+        from hipgp_amd import kuf
+        key = (x.data_ptr(), tuple(x.shape), x.dtype)
+        if key not in win["plans"]:
+            # x is kept with the plan so that its address stays its own while the key lives
+            win["plans"][key] = (kuf.WindowPlan.make(self.kernel, self.xgrids, x, params, win["tol"]), x)
+        return win["plans"][key][0]
+
     def _kuf_product(self, x, W, integrated_obs, estimator, samps, mc_offset, batch_size):
         """Knm(x) W^T, (N, nw) on the device, for weight rows W (nw, M): the fused products of
         `hipgp_amd.kuf` where they apply (Knm never stored), else `_make_grams(piece)[0] @ W^T` over
@@ -456,7 +490,10 @@ class ToeplitzInducingGP(SviGP):
         from hipgp_amd import kuf
         params = self.get_kernel_params()
         out = None
-        if not integrated_obs:
+        plan = None if integrated_obs else self._window_plan(x, params)
+        if plan is not None:
+            out = kuf.kuf_grid_matvec_win(plan, W)
+        elif not integrated_obs:
             out = kuf.kuf_grid_matvec(self.kernel, self.xgrids, x, params, W)
         elif estimator == "analytic":
             out = kuf.kuf_semi_sqexp_matvec(self.kernel, self.xgrids, x, params, W)
@@ -480,10 +517,15 @@ class ToeplitzInducingGP(SviGP):
         caller's `weights`, kept from an earlier call), the product by `_kuf_product`.  The sd is
         not available this way (it needs kn itself): use `predict`.  With the "mc-biased" estimator
         and no `mc_offset` the fused product draws one offset for all of x, the fallback one per
-        piece, as `_make_grams` would."""
+        piece, as `_make_grams` would.
+
+        With a support tolerance t (the model's `kuf_support_tol`, else env HGP_KUF_SUPPORT_TOL; see
+        `kuf.support_radius`) point observations take the windowed product: every point sums only the
+        nodes within the kernel's reach, and the mean moves by at most t sig2 sum_j |alpha_j|.  With
+        integrated_obs=True a tolerance raises NotImplementedError."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
-        with torch.no_grad():
+        with torch.no_grad(), self._windowed(None, integrated_obs):
             x = x.to(self.xgrids[0].device)
             if weights is None:
                 weights = self.mean_weights(maxiter_cg=maxiter_cg, Kmm=Kmm)
@@ -508,7 +550,10 @@ class ToeplitzInducingGP(SviGP):
         from hipgp_amd import kuf
         params = self.get_kernel_params()
         out = None
-        if not integrated_obs:
+        plan = None if integrated_obs else self._window_plan(x, params)
+        if plan is not None:
+            out = kuf.kuf_grid_rmatvec_win(plan, C)
+        elif not integrated_obs:
             out = kuf.kuf_grid_rmatvec(self.kernel, self.xgrids, x, params, C)
         elif estimator == "analytic":
             out = kuf.kuf_semi_sqexp_rmatvec(self.kernel, self.xgrids, x, params, C)
@@ -550,10 +595,17 @@ class ToeplitzInducingGP(SviGP):
         Returns MeanFit(weights, qm, iters, relres): weights = beta as a (1, M) device row, what
         `predict_mean(x, weights=...)` takes (K^-1 R qm = beta); qm = R^T beta (M', 1); relres the
         recurrence's last |r| / |b|.  update=True writes the mean into the model as `batch_solve`
-        does (theta1 = lam qm with lam = -2 theta2 as it stands, or global_m = qm)."""
+        does (theta1 = lam qm with lam = -2 theta2 as it stands, or global_m = qm).
+
+        With a support tolerance t (the model's `kuf_support_tol`, else env HGP_KUF_SUPPORT_TOL) and
+        point observations both Kuf products are the windowed ones, exact transposes of each other on
+        one `kuf.WindowPlan` built here once (the fp64 refinement builds its own on the fp64 points,
+        with the same radius): the system solved is the one with Kuf replaced by its windowed part,
+        every entry of which is within t sig2 of the dense one.  With integrated_obs=True a tolerance
+        raises NotImplementedError."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
-        with torch.no_grad():
+        with torch.no_grad(), self._windowed(None, integrated_obs):
             dev = self.xgrids[0].device
             if Kmm is None:
                 Kmm = self.toeplitz()
@@ -651,10 +703,13 @@ class ToeplitzInducingGP(SviGP):
         These are draws of the PROJECTED process K_xu K^-1 u with u = R v the inducing values: their
         mean is `predict`'s mean and their variance is the kn S kn term of its variance.  They
         exclude the residual `ktilde` = Knn - |kn|^2 that `predict`'s sd adds, so between inducing
-        points they are smoother and narrower than draws of f itself."""
+        points they are smoother and narrower than draws of f itself.
+
+        A support tolerance (`kuf_support_tol` / HGP_KUF_SUPPORT_TOL) windows the product as in
+        `predict_mean`."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
-        with torch.no_grad():
+        with torch.no_grad(), self._windowed(None, integrated_obs):
             x = x.to(self.xgrids[0].device)
             v = self.variational_draws(n, eps=eps, generator=generator)
             alpha = self.mean_weights(v, maxiter_cg=maxiter_cg, Kmm=Kmm)
@@ -711,7 +766,7 @@ class ToeplitzInducingGP(SviGP):
         return out.mul_(beta).add_(acc) if beta != 0 else out.copy_(acc)
 
     def predict_samples(self, x, n, nfeat=4096, eps=None, features=None, prior_w=None, nugget_eps=None,
-                        generator=None, maxiter_cg=50, Kmm=None, integrated_obs=False):
+                        generator=None, maxiter_cg=50, Kmm=None, integrated_obs=False, support_tol=None):
         """n joint draws of f ITSELF at the points x, (n, N) on the CPU like `predict_draws`, by
         pathwise conditioning: f(x) = f_prior(x) + Knm(x) K^-1 (R v - f_prior(U) - sqrt(jitter) xi)
         with f_prior a random-Fourier-feature draw of the prior and v = qm + S^{1/2} eps
@@ -731,7 +786,10 @@ class ToeplitzInducingGP(SviGP):
         `hipgp_amd.rff.spectral_features` returns them, prior_w (n, F) and nugget_eps (n, M)
         standard normal.  What is not given is drawn with `generator`.  Point observations and
         whitened_type='ziggy' only (integrated_obs=True raises: the feature prior is a prior of point
-        values); SqExp and Matern kernels with a scalar ell (no Gneiting, no ARD)."""
+        values); SqExp and Matern kernels with a scalar ell (no Gneiting, no ARD).
+
+        support_tol (None: the model's `kuf_support_tol`, else env HGP_KUF_SUPPORT_TOL) windows the
+        Kuf product alone, as in `predict_mean`; the feature products are unchanged."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
         if integrated_obs:
@@ -774,7 +832,8 @@ class ToeplitzInducingGP(SviGP):
             b = b.contiguous().sub_(xi, alpha=float(np.sqrt(self.jitter_val)))
             b = self._rff_product(None, omega, phase, W, -scale, transposed=True, out=b, beta=1.0)
             alpha = self._solve_rows(Kmm, b, maxiter_cg, 1e-8)
-            out = self._kuf_product(x, alpha, False, "analytic", 10, None, None).contiguous()
+            with self._windowed(support_tol, False):
+                out = self._kuf_product(x, alpha, False, "analytic", 10, None, None).contiguous()
             out = self._rff_product(x, omega, phase, W, scale, out=out, beta=1.0)
             return out.t().contiguous().cpu().detach()
 

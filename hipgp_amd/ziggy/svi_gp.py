@@ -38,6 +38,28 @@ class SviGP(nn.Module):
         # the fused Kuf backward for kernel hyper-parameter learning (see _make_grams):
         # True / False, or None to read HGP_KUF_GRAD (default off)
         self.kuf_grad = None
+        # the windowed Kuf products of predict_mean / predict_draws / predict_samples / fit_mean
+        # (`hipgp_amd.kuf.WindowPlan`): a tolerance in (0, 1), or None to read HGP_KUF_SUPPORT_TOL
+        # (default unset: the dense products)
+        self.kuf_support_tol = None
+        self._win = None       # {"tol", "plans"} while one of those methods runs with a tolerance
+
+    def _kuf_support_tol(self, support_tol=None):
+        """The truncation tolerance of the windowed Kuf products, or None for the dense ones: the
+        argument, else the attribute `kuf_support_tol`, else env HGP_KUF_SUPPORT_TOL (unset, empty
+        or 0: none)."""
+        tol = support_tol
+        if tol is None:
+            tol = getattr(self, "kuf_support_tol", None)
+        if tol is None:
+            env = os.environ.get("HGP_KUF_SUPPORT_TOL", "")
+            tol = float(env) if env not in ("", "0") else None
+        if tol is None:
+            return None
+        tol = float(tol)
+        if not (0. < tol < 1.):
+            raise ValueError(f"the support tolerance must lie in (0, 1), got {tol}")
+        return tol
 
     def _kuf_grad_route(self, params):
         """True when `_make_grams` should try the `_ad` kernels of `hipgp_amd.kuf`: the knob

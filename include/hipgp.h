@@ -420,6 +420,51 @@ int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void
                                const void* x, int64_t nobs, double sig2, double ell,
                                const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream);
 
+/* hgp_kuf_grid_matvec over a WINDOW of pairs, for kernels far shorter than the grid:
+ *   out[n, s] = sum_{j in window(n)} k(x_n, u_j) w[s, j];  dtype, kind, ndim, grids, x, w, out as there.
+ * Pair (n, j) is in the window iff fabs(x[n][a] - g_a[j_a]) <= rho on every axis a, evaluated in
+ * dtype with rho rounded once to dtype: a box of index ranges [lo_a, hi_a), found by binary search
+ * on the axis coordinates, which must be strictly increasing.  With rho the distance from which
+ * k(r) <= tol sig2 on, every dropped pair is farther than rho, so per output
+ *   |dense - windowed| <= tol sig2 sum_j |w[s, j]|.
+ * A point farther than rho from the grid's hull on some axis has an empty window: exact zeros.
+ * Work is nobs times the window's size.  One wave per point, lanes across the last-axis range, a
+ * loop over the outer rows of the box; a lane adds its products of a row in dtype, the rows in
+ * fp64, the lanes by a fixed xor butterfly; weight rows in groups of at most 8.  No atomics, no
+ * scratch: the same bits on every call with the same arguments.
+ * nobs = 0 or nw = 0: nothing written, 0 returned.  HGP_E_ARG (before any HIP call): null pointer,
+ * bad dtype / kind / ndim, a grid size < 1, nobs / nw < 0, rho negative or not finite.  HGP_E_HIP:
+ * the launch failed. */
+int hgp_kuf_grid_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                            const void* x, int64_t nobs, double sig2, double ell, double rho,
+                            const void* w, int64_t nw, void* out, void* hip_stream);
+
+/* hgp_kuf_grid_rmatvec over the same window:
+ *   out[s, j] = sum_{n: (n, j) in window} c[s, n] k(x_n, u_j);  c, out as hgp_kuf_grid_rmatvec.
+ * The same set of pairs and the same element values, bit for bit, as hgp_kuf_grid_matvec_win: the
+ * two are exact transposes, which a conjugate-gradient solve on K + Kuf^T diag(iv) Kuf needs.
+ * A gather: a block owns a tile of mesh points and visits only the bins of observations that can
+ * reach it.  order (nobs, device int64) lists the observations sorted stably by bin; bin_start
+ * (total bins + 1, device int64) are the offsets of the bins in that list.  The bin of x on axis a
+ * is (number of nodes g_a[i] <= x_a) / tile[a], the bins are numbered in C order over the axes with
+ * nbins[a] per axis; tile and nbins come from hgp_kuf_win_bins.  Products are added in dtype over
+ * chunks of at most 256 staged observations, the chunks in fp64, in the order of the list: no
+ * atomics, the same bits on every call with the same arguments.  The kernel skips any order[k]
+ * outside [0, nobs) and any range of bin_start outside 0 <= s0 <= s1 <= nobs, so a wrong list gives
+ * wrong sums and never an access out of bounds (bin_start must still hold total bins + 1 entries).
+ * nobs = 0: out is set to zero (order and bin_start are not read); nc = 0: nothing written; both
+ * return 0.  Errors as hgp_kuf_grid_matvec_win, and null order / bin_start with nobs > 0. */
+int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                             const void* x, int64_t nobs, double sig2, double ell, double rho,
+                             const void* c, int64_t nc, const int64_t* order, const int64_t* bin_start,
+                             void* out, void* hip_stream);
+
+/* The tile and bin geometry hgp_kuf_grid_rmatvec_win assumes (host only, no HIP call): tile_out[a]
+ * mesh points of a tile, and cells of a bin, along axis a; nbins_out[a] = m[a] / tile_out[a] + 1
+ * bins, which cover the cells 0 .. m[a].  Both arrays have 3 entries; axes >= ndim get 1 and 1.
+ * HGP_E_ARG: ndim outside 1..3, a null pointer, a grid size < 1. */
+int hgp_kuf_win_bins(int ndim, const int64_t* m, int64_t* tile_out, int64_t* nbins_out);
+
 /* Product with random Fourier features, never stored:
  *   acc[i, s] = scale * sum_f w[s, f] cos(2 pi (omega_f . p_i + phase_f)),   out = beta * out + acc,
  *   omega: (nfeat, ndim) rows and phase: (nfeat), both in REVOLUTIONS (radians / 2 pi; the caller

@@ -110,6 +110,22 @@ int main() {
                                  nullptr) == 0);
   EXPECT(hgp_kuf_semi_sqexp_rmatvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, -2, 0, buf, nullptr) == HGP_E_ARG);
   EXPECT(hgp_kuf_semi_sqexp_rmatvec(HGP_F64, 2, m3, grids, buf, 3, 1., 1., buf, 0, 0, buf, nullptr) == 0);
+  // the windowed products: refused, or nothing to do, before any HIP call; the bin geometry on the host
+  {
+    int64_t idx[8] = {0}, tile[3] = {0}, nbins[3] = {0};
+    EXPECT(hgp_kuf_grid_matvec_win(HGP_F32, HGP_KERN_GNEITING, 2, m3, grids, buf, 3, 1., 1., .5, buf, 2, buf, nullptr) == HGP_E_ARG);
+    EXPECT(hgp_kuf_grid_matvec_win(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., -.5, buf, 2, buf, nullptr) == HGP_E_ARG);
+    EXPECT(hgp_kuf_grid_matvec_win(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., .5, nullptr, 2, buf, nullptr) == HGP_E_ARG);
+    EXPECT(hgp_kuf_grid_matvec_win(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 0, 1., 1., .5, buf, 2, buf, nullptr) == 0);
+    EXPECT(hgp_kuf_grid_rmatvec_win(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., .5, buf, 2, nullptr, idx, buf, nullptr) == HGP_E_ARG);
+    EXPECT(hgp_kuf_grid_rmatvec_win(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., .5, buf, 2, idx, nullptr, buf, nullptr) == HGP_E_ARG);
+    EXPECT(hgp_kuf_grid_rmatvec_win(HGP_F32, HGP_KERN_SQEXP, 2, mbad, grids, buf, 3, 1., 1., .5, buf, 2, idx, idx, buf, nullptr) == HGP_E_ARG);
+    EXPECT(hgp_kuf_grid_rmatvec_win(HGP_F32, HGP_KERN_SQEXP, 2, m3, grids, buf, 3, 1., 1., .5, nullptr, 0, nullptr, nullptr, nullptr, nullptr) == 0);
+    EXPECT(hgp_kuf_win_bins(2, m3, tile, nbins) == 0 && tile[0] * tile[1] * tile[2] == 256);
+    EXPECT(nbins[0] == m3[0] / tile[0] + 1 && nbins[1] == m3[1] / tile[1] + 1 && nbins[2] == 1);
+    EXPECT(hgp_kuf_win_bins(2, mbad, tile, nbins) == HGP_E_ARG);
+    EXPECT(hgp_kuf_win_bins(2, m3, nullptr, nbins) == HGP_E_ARG);
+  }
   // the Fourier-feature product: refused or empty before any HIP call
   EXPECT(hgp_rff_matvec(HGP_F32, 2, nullptr, nullptr, buf, 3, buf, buf, 5, buf, 2, 1., 0, 0., 0, nullptr, nullptr) == HGP_E_ARG);
   EXPECT(hgp_rff_matvec(HGP_F32, 2, m3, grids, buf, 3, buf, buf, 5, buf, 2, 1., 0, 0., 0, buf, nullptr) == HGP_E_ARG);
