@@ -39,6 +39,8 @@ EXPORTS = (
     "hgp_plan_is_separable", "hgp_separable_detect", "hgp_rff_matvec", "hgp_rff_line_matvec",
     "hgp_plan_band_radius", "hgp_band_radius", "hgp_plan_band_fused", "hgp_band_fused_tile",
     "hgp_kuf_grid_matvec_win", "hgp_kuf_grid_rmatvec_win", "hgp_kuf_win_bins",
+    "hgp_kuf_semi_mc_matvec_win", "hgp_kuf_semi_sqexp_matvec_win",
+    "hgp_kuf_semi_mc_rmatvec_win", "hgp_kuf_semi_sqexp_rmatvec_win",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -108,6 +110,14 @@ def lib():
         "hgp_kuf_grid_rmatvec_win": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, vp, i64, vp,
                                            vp, vp, vp]),
         "hgp_kuf_win_bins": (i32, [i32, pi64, pi64, pi64]),
+        "hgp_kuf_semi_mc_matvec_win": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, i32, vp,
+                                             vp, i64, vp, i64, vp, vp]),
+        "hgp_kuf_semi_sqexp_matvec_win": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, vp, i64,
+                                                vp, i64, vp, vp]),
+        "hgp_kuf_semi_mc_rmatvec_win": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, i32, vp,
+                                              vp, i64, vp, i64, vp, vp]),
+        "hgp_kuf_semi_sqexp_rmatvec_win": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, vp, i64,
+                                                 vp, i64, vp, vp]),
         "hgp_rff_matvec": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, vp, vp, i64, vp, i64, dbl, i32, dbl, i64,
                                  vp, vp]),
         "hgp_rff_line_matvec": (i32, [i32, i32, vp, i64, vp, vp, i64, vp, i64, dbl, i32, dbl, i64, vp, vp]),

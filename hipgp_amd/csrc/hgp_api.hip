@@ -2726,6 +2726,69 @@ int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, co
   return 0;
 }
 
+// the windowed line-integral products: the dense entries' checks, rho, the kernel and the piece counts
+static int check_line_win(int kind, double rho, const int* pieces, int64_t npieces, int64_t nobs) {
+  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // no Gneiting
+  HGP_TRY(check_win_rho(rho));
+  if (npieces != nobs) return fail(HGP_E_ARG, "pieces must hold nobs entries");
+  if (nobs > 0 && pieces == nullptr) return fail(HGP_E_ARG, "null pieces");
+  return 0;
+}
+
+int hgp_kuf_semi_mc_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                               const void* x, int64_t nobs, double sig2, double ell, double rho, int npts,
+                               const void* u, const int* pieces, int64_t npieces, const void* w, int64_t nw,
+                               void* out, void* hip_stream) {
+  HGP_TRY(check_line_win(kind, rho, pieces, npieces, nobs));
+  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
+  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
+  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
+  if (c != 0) return c > 0 ? 0 : c;
+  hipError_t e = kuf_line_matvec_win(dtype, 1, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, w,
+                                     nw, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_matvec_win: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_sqexp_matvec_win(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                                  int64_t nobs, double sig2, double ell, double rho, const int* pieces,
+                                  int64_t npieces, const void* w, int64_t nw, void* out, void* hip_stream) {
+  HGP_TRY(check_line_win(HGP_KERN_SQEXP, rho, pieces, npieces, nobs));
+  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
+  if (c != 0) return c > 0 ? 0 : c;
+  hipError_t e = kuf_line_matvec_win(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, 0, nullptr,
+                                     pieces, w, nw, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_matvec_win: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_mc_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                                const void* x, int64_t nobs, double sig2, double ell, double rho, int npts,
+                                const void* u, const int* pieces, int64_t npieces, const void* c, int64_t nc,
+                                void* out, void* hip_stream) {
+  HGP_TRY(check_line_win(kind, rho, pieces, npieces, nobs));
+  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
+  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  hipError_t e = kuf_line_rmatvec_win(dtype, 1, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, c,
+                                      nc, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_rmatvec_win: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int hgp_kuf_semi_sqexp_rmatvec_win(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                                   int64_t nobs, double sig2, double ell, double rho, const int* pieces,
+                                   int64_t npieces, const void* c, int64_t nc, void* out, void* hip_stream) {
+  HGP_TRY(check_line_win(HGP_KERN_SQEXP, rho, pieces, npieces, nobs));
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  hipError_t e = kuf_line_rmatvec_win(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, 0,
+                                      nullptr, pieces, c, nc, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_rmatvec_win: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_kuf_win_bins(int ndim, const int64_t* m, int64_t* tile_out, int64_t* nbins_out) {
   if (ndim < 1 || ndim > 3 || m == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m non-null");
   if (tile_out == nullptr || nbins_out == nullptr) return fail(HGP_E_ARG, "null tile_out / nbins_out");

@@ -117,6 +117,17 @@ hipError_t kuf_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, cons
                            int64_t nobs, double sig2, double ell, double rho, const void* c, int64_t nc,
                            const int64_t* order, const int64_t* bin_start, void* out, hipStream_t s);
 void kuf_win_geometry(int ndim, const int64_t* m, int64_t* tile, int64_t* nbins);
+// the two line-integral products over the window of a line: the nodes within rho of a piece of its segment
+// (hgp_kuf_line_win.hip); mode 1 semi-mc, 2 semi-sqexp; pieces: nobs device ints; matvec: nobs > 0, nw > 0;
+// rmatvec: nobs >= 0 (0: out zeroed), nc > 0
+hipError_t kuf_line_matvec_win(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m,
+                               const void* const* grids, const void* x, int64_t nobs, double sig2, double ell,
+                               double rho, int npts, const void* u, const int* pieces, const void* w, int64_t nw,
+                               void* out, hipStream_t s);
+hipError_t kuf_line_rmatvec_win(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m,
+                                const void* const* grids, const void* x, int64_t nobs, double sig2, double ell,
+                                double rho, int npts, const void* u, const int* pieces, const void* c, int64_t nc,
+                                void* out, hipStream_t s);
 // out = beta out + scale w cos(2 pi (omega . p + phase)) without the features (hgp_rff.hip); x == nullptr: the points
 // are the mesh of (m, grids), else npoints rows of x; npoints > 0, nfeat > 0, nw > 0, nsplit >= 0 (0: chosen here)
 hipError_t rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t npoints,

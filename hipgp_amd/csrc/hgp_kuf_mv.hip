@@ -26,13 +26,14 @@
 #include <stdint.h>
 
 #include "hgp_kuf_eval.hpp"
+#include "hgp_kuf_semi.hpp"
 
 namespace hgp {
 
 constexpr int MV_TILE = 64;       // points per block of the point kernel (one wave)
 constexpr int MV_UNIT = 64;       // grid points per unit of the split
 constexpr int MV_RUN = 256;       // longest run summed in the tensor dtype
-constexpr int MV_THREADS = 256;   // block of the line-integral kernels
+constexpr int MV_THREADS = SEMI_THREADS;   // block of the line-integral kernels
 constexpr int MV_MIN_UNITS = 4;   // nsplit = 0 leaves a slice at least this many units
 
 template <typename T, int KIND, int NW>
@@ -110,41 +111,6 @@ __global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __r
   }
 }
 
-// out[n, s] = sum over the slices, in slice order, of part[slice][n][s]  (s < nwv of NW slots)
-template <typename T>
-__global__ __launch_bounds__(256) void k_kuf_mv_finish(const double* __restrict__ part, int nsplit, int64_t B, int NW,
-                                                      int nwv, T* __restrict__ out, int64_t ldo) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= B * NW) return;
-  const int64_t n = t / NW;
-  const int s = (int)(t % NW);
-  if (s >= nwv) return;
-  double a = 0;
-  for (int k = 0; k < nsplit; ++k) a += part[((int64_t)k * B + n) * NW + s];
-  out[n * ldo + s] = (T)a;
-}
-
-// the NW sums of a block in a fixed order: lanes by the xor butterfly, waves in wave order
-template <int NW>
-__device__ __forceinline__ void mv_block_sum(double (&a)[NW], double* __restrict__ dst, int nwv) {
-  __shared__ double red[MV_THREADS / 64][NW];
-#pragma unroll
-  for (int s = 0; s < NW; ++s)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a[s] += __shfl_xor(a[s], off, 64);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int s = 0; s < NW; ++s) red[wv][s] = a[s];
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nwv) {
-    double t = 0;
-    for (int k = 0; k < MV_THREADS / 64; ++k) t += red[k][threadIdx.x];
-    dst[threadIdx.x] = t;
-  }
-}
-
 // MODE 1: the Monte-Carlo line integral of k_kuf_semi_mc; MODE 2: the analytic SqExp one of
 // k_kuf_semi_sqexp.  Block (n, slice of outer indices); element values formed as the forwards do.
 template <typename T, int MODE, int NW>
@@ -169,83 +135,54 @@ __global__ __launch_bounds__(MV_THREADS) void k_kuf_semi_mv(KufGrid g, const T* 
   double acc[NW];
 #pragma unroll
   for (int s = 0; s < NW; ++s) acc[s] = 0;
-  T xn2 = 0;
-  for (int ax = 0; ax < d; ++ax) xn2 += x[n * d + ax] * x[n * d + ax];
-  const T dist = sqrt(xn2);
+  const T dist = semi_dist<T>(x, n, d);
 
   if (MODE == 1) {
     const bool sq = scaled_dist(kind);
-    const T uoff = u[0] * (T)(1.0 / (double)npts);
+    const T uoff = semi_mc_offset<T>(u, npts);
     for (int64_t o = o0; o < o1; ++o) {                       // the same trip count for every thread
       __syncthreads();                                        // the last row's readers are done
       for (int a = threadIdx.x; a < npts; a += MV_THREADS) {
-        const T al = (T)a / (T)npts + uoff;
-        auto sqd = [&](int ax, int64_t ia) -> T {
-          T dv = reinterpret_cast<const T*>(g.g[ax])[ia] - x[n * d + ax] * al;
-          if (sq) dv = dv / ell;
-          return dv * dv;
-        };
-        T so = 0;
-        if (d == 2) so = sqd(0, o);
-        if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
-        so_s[a] = so;
+        const T al = semi_mc_alpha<T>(a, npts, uoff);
+        so_s[a] = semi_mc_outer<T>(d, [&](int ax) -> T {
+          const int64_t ia = d == 2 ? o : (ax == 0 ? o / g.m[1] : o % g.m[1]);
+          return semi_mc_sqd<T>(reinterpret_cast<const T*>(g.g[ax])[ia], x[n * d + ax], al, sq, ell);
+        });
         xl_s[a] = x[n * d + d - 1] * al;
       }
       __syncthreads();
       for (int64_t i = threadIdx.x; i < inner; i += MV_THREADS) {
-        const T ui = gl[i];
-        T ka = 0;
-        for (int a = 0; a < npts; ++a) {
-          T dv = ui - xl_s[a];
-          if (sq) dv = dv / ell;
-          const T sv = (d == 1) ? dv * dv : so_s[a] + dv * dv;
-          ka += kern_eval<T>(kind, sv, sig2, ell, kp);
-        }
-        const T kv = ka / (T)npts * dist;
+        const T kv = semi_mc_elem<T>(kind, d, gl[i], npts, sq, sig2, ell, kp, dist, [&](int a, T& xl, T& so) {
+          xl = xl_s[a];
+          so = so_s[a];
+        });
 #pragma unroll
         for (int s = 0; s < NW; ++s) acc[s] += (double)(kv * wp[s][o * inner + i]);
       }
     }
   } else {
     const T sinv = (T)1 / (ell * ell);
-    const T sqrt2 = (T)1.4142135623730950488, sqrt2pi = (T)2.5066282746310005024;
     T xs[3];
-    T av = 0;
-    for (int ax = 0; ax < d; ++ax) {
-      const T xv = x[n * d + ax];
-      xs[ax] = xv * sinv;
-      av += xs[ax] * xv;
-    }
+    const T av = semi_sq_line<T>(x, n, d, sinv, xs);
     const T scale = sqrt((T)1 / av);
     for (int64_t o = o0; o < o1; ++o) {
       int64_t oi[2] = {0, 0};
       if (d == 2) oi[0] = o;
       if (d == 3) { oi[0] = o / g.m[1]; oi[1] = o % g.m[1]; }
-      T bo = 0, co = 0;
-      for (int ax = 0; ax < d - 1; ++ax) {
-        const T ua = reinterpret_cast<const T*>(g.g[ax])[oi[ax]];
-        bo += xs[ax] * ua;
-        co += (ua * sinv) * ua;
-      }
+      T bo, co;
+      semi_sq_outer<T>(d, xs, sinv, [&](int ax) -> T { return reinterpret_cast<const T*>(g.g[ax])[oi[ax]]; }, bo, co);
       for (int64_t i = threadIdx.x; i < inner; i += MV_THREADS) {
-        const T ui = gl[i];
-        const T b = (d == 1) ? xs[0] * ui : bo + xs[d - 1] * ui;
-        const T c = (d == 1) ? (ui * sinv) * ui : co + (ui * sinv) * ui;
-        const T loc = b / av;
-        const T coef = sig2 * exp((b * b) / ((T)2 * av) - c / (T)2) * sqrt2pi * scale;
-        const T ca = (T)0.5 * ((T)1 + erf(((T)1 - loc) / (scale * sqrt2)));
-        const T cb = (T)0.5 * ((T)1 + erf(((T)0 - loc) / (scale * sqrt2)));
-        const T kv = coef * (ca - cb) * dist;
+        const T kv = semi_sq_elem<T>(d, bo, co, xs[d - 1], gl[i], sinv, av, scale, sig2, dist);
 #pragma unroll
         for (int s = 0; s < NW; ++s) acc[s] += (double)(kv * wp[s][o * inner + i]);
       }
     }
   }
   if (part != nullptr) {
-    mv_block_sum<NW>(acc, part + (slice * B + n) * NW, NW);
+    semi_block_sum<NW>(acc, part + (slice * B + n) * NW, NW);
   } else {
     __shared__ double row[NW];
-    mv_block_sum<NW>(acc, row, nwv);
+    semi_block_sum<NW>(acc, row, nwv);
     __syncthreads();
     if ((int)threadIdx.x < nwv) out[n * ldo + threadIdx.x] = (T)row[threadIdx.x];
   }

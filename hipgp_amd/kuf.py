@@ -22,6 +22,9 @@ operator K + Knm^T diag(iv) Knm behind `ToeplitzInducingGP.fit_mean`.
 The point-observation pair of those also over a window, for kernels far shorter than the grid:
 `support_radius` (the truncation rule), `WindowPlan`, `kuf_grid_matvec_win` / `kuf_grid_rmatvec_win`
 (hgp_kuf_grid_matvec_win / hgp_kuf_grid_rmatvec_win), within tol * sig2 * sum |w| of the dense ones.
+The line-integral pairs over the window of a line, a tube around its segment: `LineWindowPlan`,
+`kuf_semi_mc_matvec_win` / `kuf_semi_mc_rmatvec_win`, `kuf_semi_sqexp_matvec_win` /
+`kuf_semi_sqexp_rmatvec_win` (hgp_kuf_semi_*_win).
 """
 import ctypes
 
@@ -455,6 +458,124 @@ def kuf_grid_rmatvec_win(plan, C):
                                          ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], ptr(order), ptr(start),
                                          ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
     return out
+
+
+# ---- the two line-integral products over the window of a line: a tube around its segment --------
+# Line n is the segment from the origin to x_n.  It is cut into pieces[n] equal pieces; a node is in
+# the line's window iff it lies in the bounding box of some piece widened by rho on every axis, which
+# holds every node within Chebyshev distance rho of the segment.  Per output the windowed product is
+# within tol * sig2 * |x_n| * sum |w| (transposed: tol * sig2 * sum_n |c_n| |x_n|) of the dense one.
+
+LINE_MAX_PIECES = 64
+
+
+def line_pieces(x, rho):
+    """Pieces per line, int32 (nobs,): about one per rho of the line's largest |x_a|, at least 1 and
+    at most LINE_MAX_PIECES (longer pieces beyond: a larger window, still a superset of the tube).
+    x = 0 and NaN rows get 1."""
+    xa = x.detach().abs().amax(dim=1).double()
+    p = torch.ceil(xa / float(rho)) if float(rho) > 0 else torch.full_like(xa, float(LINE_MAX_PIECES))
+    p = torch.nan_to_num(p, nan=1., posinf=float(LINE_MAX_PIECES))
+    return p.clamp_(1, LINE_MAX_PIECES).to(torch.int32).contiguous()
+
+
+class LineWindowPlan:
+    """What the windowed line-integral products share for one set of lines x against one grid: the
+    radius rho (`support_radius(kernel, params, tol)`, or the given `rho`), the contiguous grids and
+    x, and the pieces per line (`line_pieces`), computed once so that both products read the same
+    numbers.  x, the grids and the kernel parameters must not change while the plan is in use.  The
+    constructor raises ValueError where the products do not apply; `make` returns None there."""
+
+    def __init__(self, kernel, xgrids, x, params, tol, rho=None):
+        a = _grid_call_args(kernel, xgrids, x, params) if torch.is_tensor(x) and xgrids is not None else None
+        if rho is None:
+            rho = support_radius(kernel, params, tol)
+        if a is None or rho is None or not (float(rho) >= 0) or float(rho) == float("inf"):
+            raise ValueError("the windowed line-integral Kuf products do not apply: they take SqExp / Matern(1/2, "
+                             "3/2, 5/2) with a scalar ell, a tolerance in (0, 1), device lines (nobs, D <= 3) in "
+                             "fp32 / fp64 and no graph to x, sig2 or ell")
+        self.kind, self.sig2, self.ell, self.grids, self.x, self.M = a
+        self.kernel_dtype = getattr(kernel, "dtype", x.dtype)
+        self.rho, self.tol = float(rho), tol
+        self.dims = [g.numel() for g in self.grids]
+        self.pieces = line_pieces(self.x, self.rho)
+
+    @classmethod
+    def make(cls, kernel, xgrids, x, params, tol, rho=None):
+        """The plan, or None where `support_radius` or the fused grid kernels decline."""
+        try:
+            return cls(kernel, xgrids, x, params, tol, rho=rho)
+        except ValueError:
+            return None
+
+    @property
+    def nobs(self):
+        return self.x.shape[0]
+
+
+def _line_win_call(plan, name, rows, out, npts=None, u=None):
+    """One hgp_kuf_semi_*_win entry: `rows` are the weight or coefficient rows."""
+    x = plan.x
+    m, ptrs = _grid_ptrs(plan.grids)
+    head = [_lib.dtype_code(x.dtype)] + ([plan.kind] if npts is not None else []) + \
+           [len(plan.grids), m, ptrs, ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho]
+    if npts is not None:
+        if u is None:
+            u = torch.rand(1, dtype=plan.kernel_dtype, device=x.device)         # kernels.py:28-29
+        u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
+        head += [int(npts), ctypes.c_void_p(u.data_ptr())]
+    check(getattr(lib(), name)(*head, ctypes.c_void_p(plan.pieces.data_ptr()), plan.pieces.shape[0],
+                               ctypes.c_void_p(rows.data_ptr()), rows.shape[0], ctypes.c_void_p(out.data_ptr()),
+                               _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_semi_mc_matvec_win(plan, W, npts, u=None):
+    """The windowed kuf_semi_mc(...) @ W^T, (nobs, nw), for the plan's lines
+    (hgp_kuf_semi_mc_matvec_win): W is (nw, M) or (M,), the offset draw `u` as in `kuf_semi_mc`.
+    Within plan.tol * sig2 * |x_n| * sum_j |W[s, j]| of `kuf_semi_mc_matvec` per output; a line with
+    an empty window (x = 0 included) gives exact zeros.  None where W carries a graph."""
+    Wc = _matvec_weights(W, plan.x, plan.M)
+    if Wc is None:
+        return None
+    out = torch.empty((plan.nobs, Wc.shape[0]), dtype=plan.x.dtype, device=plan.x.device)
+    return _line_win_call(plan, "hgp_kuf_semi_mc_matvec_win", Wc, out, npts=npts, u=u)
+
+
+def kuf_semi_sqexp_matvec_win(plan, W):
+    """The windowed kuf_semi_sqexp(...) @ W^T (hgp_kuf_semi_sqexp_matvec_win); SqExp only (None
+    otherwise).  A line with x = 0 gives zeros where the dense product gives NaN."""
+    if plan.kind != _lib.KERN_SQEXP:
+        return None
+    Wc = _matvec_weights(W, plan.x, plan.M)
+    if Wc is None:
+        return None
+    out = torch.empty((plan.nobs, Wc.shape[0]), dtype=plan.x.dtype, device=plan.x.device)
+    return _line_win_call(plan, "hgp_kuf_semi_sqexp_matvec_win", Wc, out)
+
+
+def kuf_semi_mc_rmatvec_win(plan, C, npts, u=None):
+    """The windowed C @ kuf_semi_mc(...), (nc, M), for the plan's lines (hgp_kuf_semi_mc_rmatvec_win):
+    the exact transpose of `kuf_semi_mc_matvec_win` on the same plan and offset (the same pairs, the
+    same element values); within plan.tol * sig2 * sum_n |C[s, n]| |x_n| of the dense product per
+    output.  No lines: zeros.  None where C carries a graph."""
+    Cc = _rmatvec_coefs(C, plan.x)
+    if Cc is None:
+        return None
+    out = torch.empty((Cc.shape[0], plan.M), dtype=plan.x.dtype, device=plan.x.device)
+    return _line_win_call(plan, "hgp_kuf_semi_mc_rmatvec_win", Cc, out, npts=npts, u=u)
+
+
+def kuf_semi_sqexp_rmatvec_win(plan, C):
+    """The windowed C @ kuf_semi_sqexp(...) (hgp_kuf_semi_sqexp_rmatvec_win), the exact transpose of
+    `kuf_semi_sqexp_matvec_win`; SqExp only (None otherwise)."""
+    if plan.kind != _lib.KERN_SQEXP:
+        return None
+    Cc = _rmatvec_coefs(C, plan.x)
+    if Cc is None:
+        return None
+    out = torch.empty((Cc.shape[0], plan.M), dtype=plan.x.dtype, device=plan.x.device)
+    return _line_win_call(plan, "hgp_kuf_semi_sqexp_rmatvec_win", Cc, out)
 
 
 def knn_doubly_diag(table, x, params):

@@ -469,6 +469,45 @@ class ToeplitzInducingGP(SviGP):
         finally:
             self._win = prev
 
+    # Line integrals have a knob of their own: the attribute `kuf_line_support_tol`, else env
+    # HGP_KUF_LINE_SUPPORT_TOL.  With it set `_kuf_product` / `_kuf_rproduct` take the windowed line
+    # products of `hipgp_amd.kuf` for integrated_obs=True ("analytic" and "mc-biased"), through one
+    # `kuf.LineWindowPlan` per (x, dtype) kept for the length of the public call; where the plan
+    # declines the dense route runs.  Unset, `self._lwin` stays None and nothing changes.
+    def _kuf_line_support_tol(self):
+        tol = getattr(self, "kuf_line_support_tol", None)
+        if tol is None:
+            env = os.environ.get("HGP_KUF_LINE_SUPPORT_TOL", "")
+            tol = float(env) if env not in ("", "0") else None
+        if tol is None:
+            return None
+        tol = float(tol)
+        if not (0. < tol < 1.):
+            raise ValueError(f"the line support tolerance must lie in (0, 1), got {tol}")
+        return tol
+
+    @contextlib.contextmanager
+    def _line_windowed(self, integrated_obs=True):
+        tol = self._kuf_line_support_tol() if integrated_obs else None
+        prev = getattr(self, "_lwin", None)
+        self._lwin = None if tol is None else {"tol": tol, "plans": {}}
+        try:
+            yield
+        finally:
+            self._lwin = prev
+
+    def _line_window_plan(self, x, params):
+        """The call's `kuf.LineWindowPlan` for the lines x (one per x and dtype), or None: no line
+        tolerance is set, or the plan declines (the dense route then runs as before)."""
+        win = getattr(self, "_lwin", None)
+        if win is None or not torch.is_tensor(x) or x.device.type != "cuda":
+            return None
+        from hipgp_amd import kuf
+        key = (x.data_ptr(), tuple(x.shape), x.dtype)
+        if key not in win["plans"]:
+            win["plans"][key] = (kuf.LineWindowPlan.make(self.kernel, self.xgrids, x, params, win["tol"]), x)
+        return win["plans"][key][0]
+
     def _window_plan(self, x, params):
         """The call's `kuf.WindowPlan` for the points x (one per x and dtype), or None: no tolerance
         is set, or the plan declines (the dense route then runs as before)."""
@@ -491,8 +530,13 @@ class ToeplitzInducingGP(SviGP):
         params = self.get_kernel_params()
         out = None
         plan = None if integrated_obs else self._window_plan(x, params)
+        lplan = self._line_window_plan(x, params) if integrated_obs else None
         if plan is not None:
             out = kuf.kuf_grid_matvec_win(plan, W)
+        elif lplan is not None and estimator == "analytic" and lplan.kind == 0:
+            out = kuf.kuf_semi_sqexp_matvec_win(lplan, W)
+        elif lplan is not None and estimator == "mc-biased":
+            out = kuf.kuf_semi_mc_matvec_win(lplan, W, samps, u=mc_offset)
         elif not integrated_obs:
             out = kuf.kuf_grid_matvec(self.kernel, self.xgrids, x, params, W)
         elif estimator == "analytic":
@@ -525,7 +569,7 @@ class ToeplitzInducingGP(SviGP):
         integrated_obs=True a tolerance raises NotImplementedError."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
-        with torch.no_grad(), self._windowed(None, integrated_obs):
+        with torch.no_grad(), self._windowed(None, integrated_obs), self._line_windowed(integrated_obs):
             x = x.to(self.xgrids[0].device)
             if weights is None:
                 weights = self.mean_weights(maxiter_cg=maxiter_cg, Kmm=Kmm)
@@ -551,8 +595,13 @@ class ToeplitzInducingGP(SviGP):
         params = self.get_kernel_params()
         out = None
         plan = None if integrated_obs else self._window_plan(x, params)
+        lplan = self._line_window_plan(x, params) if integrated_obs else None
         if plan is not None:
             out = kuf.kuf_grid_rmatvec_win(plan, C)
+        elif lplan is not None and estimator == "analytic" and lplan.kind == 0:
+            out = kuf.kuf_semi_sqexp_rmatvec_win(lplan, C)
+        elif lplan is not None and estimator == "mc-biased":
+            out = kuf.kuf_semi_mc_rmatvec_win(lplan, C, samps, u=mc_offset)
         elif not integrated_obs:
             out = kuf.kuf_grid_rmatvec(self.kernel, self.xgrids, x, params, C)
         elif estimator == "analytic":
@@ -605,7 +654,7 @@ class ToeplitzInducingGP(SviGP):
         raises NotImplementedError."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
-        with torch.no_grad(), self._windowed(None, integrated_obs):
+        with torch.no_grad(), self._windowed(None, integrated_obs), self._line_windowed(integrated_obs):
             dev = self.xgrids[0].device
             if Kmm is None:
                 Kmm = self.toeplitz()
@@ -709,7 +758,7 @@ class ToeplitzInducingGP(SviGP):
         `predict_mean`."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
-        with torch.no_grad(), self._windowed(None, integrated_obs):
+        with torch.no_grad(), self._windowed(None, integrated_obs), self._line_windowed(integrated_obs):
             x = x.to(self.xgrids[0].device)
             v = self.variational_draws(n, eps=eps, generator=generator)
             alpha = self.mean_weights(v, maxiter_cg=maxiter_cg, Kmm=Kmm)
@@ -876,7 +925,7 @@ class ToeplitzInducingGP(SviGP):
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
         from hipgp_amd import rff
-        with torch.no_grad():
+        with torch.no_grad(), self._line_windowed():
             dev = self.xgrids[0].device
             n = int(n)
             x = x.to(device=dev, dtype=self.dtype)

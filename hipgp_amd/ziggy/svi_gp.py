@@ -43,6 +43,9 @@ class SviGP(nn.Module):
         # (default unset: the dense products)
         self.kuf_support_tol = None
         self._win = None       # {"tol", "plans"} while one of those methods runs with a tolerance
+        # the same for line integrals (None: env HGP_KUF_LINE_SUPPORT_TOL, unset: the dense products)
+        self.kuf_line_support_tol = None
+        self._lwin = None
 
     def _kuf_support_tol(self, support_tol=None):
         """The truncation tolerance of the windowed Kuf products, or None for the dense ones: the

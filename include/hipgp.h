@@ -465,6 +465,59 @@ int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, co
  * HGP_E_ARG: ndim outside 1..3, a null pointer, a grid size < 1. */
 int hgp_kuf_win_bins(int ndim, const int64_t* m, int64_t* tile_out, int64_t* nbins_out);
 
+/* hgp_kuf_semi_mc_matvec over the WINDOW of a line, for kernels far shorter than the grid (the
+ * Monte-Carlo line integral of Kernel.k_semi_mc, kernels.py:19-39, summed over a tube around the
+ * segment in place of the whole mesh):
+ *   out[n, s] = sum_{j in window(n)} Kuf[n, j] w[s, j];  dtype, ndim, grids, x, npts, u, w, out as there;
+ *   kind HGP_KERN_SQEXP .. HGP_KERN_MATERN52 (HGP_KERN_GNEITING refused).
+ * Line n is the segment from the origin to x_n, cut into P = pieces[n] equal pieces (a device int
+ * array of npieces = nobs entries; a value outside 1 .. 64 is clamped).  Pair (n, j) is in the window
+ * iff node j lies in the bounding box of some piece widened by rho on every axis (lo - u <= rho and
+ * u - hi <= rho in dtype, rho rounded once to dtype; the axis coordinates must be strictly
+ * increasing).  Every node within Chebyshev distance rho of the segment is in, so with rho the
+ * distance from which k(r) <= tol sig2 on, per output
+ *   |dense - windowed| <= tol sig2 |x_n| sum_j |w[s, j]|.
+ * An in-window element has the bits hgp_kuf_semi_mc gives it.  A line with x_n = 0, with NaN
+ * coordinates or farther than rho from the grid's hull has an empty window: exact zeros.
+ * A block is one wave and owns a line and a share of the rows of its outer bounding range; per-lane
+ * fp64 sums, a fixed xor butterfly, fp64 partials per share added in order.  No atomics: the same
+ * bits on every call with the same arguments on the same device.  Scratch: at most
+ * ceil(16 CUs / nobs) * nobs * min(nw, 8) fp64, stream-ordered.
+ * nobs = 0 or nw = 0: nothing written, 0 returned.  HGP_E_ARG (before any HIP call): null pointer,
+ * bad dtype / kind / ndim / npts, a grid size < 1, nobs / nw < 0, rho negative or not finite,
+ * npieces != nobs.  HGP_E_HIP: the launch or the scratch allocation failed. */
+int hgp_kuf_semi_mc_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                               const void* x, int64_t nobs, double sig2, double ell, double rho, int npts,
+                               const void* u, const int* pieces, int64_t npieces, const void* w, int64_t nw,
+                               void* out, void* hip_stream);
+
+/* The same with the analytic SqExp line integral of hgp_kuf_semi_sqexp (SqExp.k_semi ->
+ * semi_integrated_sqe, kernels.py:80-85, 223-237): SqExp only; an in-window element has the bits
+ * hgp_kuf_semi_sqexp gives it.  Unlike the dense product a line with x_n = 0 gives zeros, not NaN. */
+int hgp_kuf_semi_sqexp_matvec_win(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                                  int64_t nobs, double sig2, double ell, double rho, const int* pieces,
+                                  int64_t npieces, const void* w, int64_t nw, void* out, void* hip_stream);
+
+/* hgp_kuf_semi_mc_rmatvec over the same window (kernels.py:19-39 transposed):
+ *   out[s, j] = sum_{n: (n, j) in window} c[s, n] Kuf[n, j];  c, out as hgp_kuf_semi_mc_rmatvec.
+ * The same set of pairs (one predicate, the same pieces) and the same element values, bit for bit,
+ * as hgp_kuf_semi_mc_matvec_win: the two are exact transposes, which a conjugate-gradient solve on
+ * K + Kuf^T diag(iv) Kuf needs.  A gather: a block owns a tile of mesh points (the tiles of
+ * hgp_kuf_win_bins) and tests all lines against it in chunks of 256, the survivors in line order;
+ * products are added in dtype over a chunk, the chunks in fp64.  The tests cost tiles * nobs cheap
+ * comparisons.  No atomics, no scratch: the same bits on every call with the same arguments.
+ * nobs = 0: out is set to zero; nc = 0: nothing written; both return 0.  Errors as the matvec. */
+int hgp_kuf_semi_mc_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                                const void* x, int64_t nobs, double sig2, double ell, double rho, int npts,
+                                const void* u, const int* pieces, int64_t npieces, const void* c, int64_t nc,
+                                void* out, void* hip_stream);
+
+/* The same with the analytic SqExp line integral (kernels.py:80-85, 223-237 transposed): the exact
+ * transpose of hgp_kuf_semi_sqexp_matvec_win. */
+int hgp_kuf_semi_sqexp_rmatvec_win(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                                   int64_t nobs, double sig2, double ell, double rho, const int* pieces,
+                                   int64_t npieces, const void* c, int64_t nc, void* out, void* hip_stream);
+
 /* Product with random Fourier features, never stored:
  *   acc[i, s] = scale * sum_f w[s, f] cos(2 pi (omega_f . p_i + phase_f)),   out = beta * out + acc,
  *   omega: (nfeat, ndim) rows and phase: (nfeat), both in REVOLUTIONS (radians / 2 pi; the caller
