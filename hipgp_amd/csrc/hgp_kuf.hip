@@ -11,7 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "hgp_kuf_eval.hpp"   // KufGrid, scaled_dist, kern_eval: shared with hgp_kuf_mv.hip
+#include "hgp_kuf_eval.hpp"   // KufGrid, scaled_dist, kern_eval: shared with every product kernel
+#include "hgp_kuf_semi.hpp"   // the line-integral element: its one definition
 
 namespace hgp {
 
@@ -66,7 +67,8 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid(KufGrid g, const T* __
 // uses it): Knm[n, j] = |x_n| * (1/npts) sum_a k(u_j, alpha_a x_n), alpha_a = a/npts + u/npts.
 // The reference builds the (M, nobs*npts, D) broadcast; here a block owns (n, outer index o):
 // the sample points alpha_a x_n and their outer-axis squared distances are block constants in
-// LDS, threads stride the last axis and sum the npts kernel values in registers.
+// LDS, threads stride the last axis and sum the npts kernel values in registers.  The arithmetic
+// is hgp_kuf_semi.hpp's (semi_mc_*), shared with the products.
 template <typename T>
 __global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_mc(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
                                                             T sig2, T ell, T kp, int npts,
@@ -85,40 +87,27 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_mc(KufGrid g, const T*
   const int64_t n = rest / outer;
   if (n >= B) return;
   const bool sq = scaled_dist(kind);
-  const T uoff = u[0] * (T)(1.0 / (double)npts);           // torch.rand(1) * delta
+  const T uoff = semi_mc_offset<T>(u, npts);
   for (int a = threadIdx.x; a < npts; a += KUF_THREADS) {
-    const T al = (T)a / (T)npts + uoff;                      // arange(npts) / npts + rand * delta
-    auto sqd = [&](int ax, int64_t ia) -> T {
-      T dv = reinterpret_cast<const T*>(g.g[ax])[ia] - x[n * d + ax] * al;   // u - alpha x
-      if (sq) dv = dv / ell;
-      return dv * dv;
-    };
-    T so = 0;
-    if (d == 2) so = sqd(0, o);
-    if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
-    so_s[a] = so;
+    const T al = semi_mc_alpha<T>(a, npts, uoff);
+    so_s[a] = semi_mc_outer<T>(d, [&](int ax) -> T {
+      const int64_t ia = d == 2 ? o : (ax == 0 ? o / g.m[1] : o % g.m[1]);
+      return semi_mc_sqd<T>(reinterpret_cast<const T*>(g.g[ax])[ia], x[n * d + ax], al, sq, ell);
+    });
     xl_s[a] = x[n * d + d - 1] * al;
   }
   __syncthreads();
-  T xn2 = 0;
-  for (int ax = 0; ax < d; ++ax) xn2 += x[n * d + ax] * x[n * d + ax];
-  const T dist = sqrt(xn2);
+  const T dist = semi_dist<T>(x, n, d);
   const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
   T* orow = out + (n * outer + o) * inner;
 #pragma unroll
   for (int k = 0; k < KUF_PER_THREAD; ++k) {
     const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
-    if (i < inner) {
-      const T ui = gl[i];
-      T acc = 0;
-      for (int a = 0; a < npts; ++a) {
-        T dv = ui - xl_s[a];
-        if (sq) dv = dv / ell;
-        const T s = (d == 1) ? dv * dv : so_s[a] + dv * dv;
-        acc += kern_eval<T>(kind, s, sig2, ell, kp);
-      }
-      orow[i] = acc / (T)npts * dist;                        // mean(dim=-1) * dists
-    }
+    if (i < inner)
+      orow[i] = semi_mc_elem<T>(kind, d, gl[i], npts, sq, sig2, ell, kp, dist, [&](int a, T& xl, T& so) {
+        xl = xl_s[a];
+        so = so_s[a];
+      });
   }
 }
 
@@ -126,7 +115,7 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_mc(KufGrid g, const T*
 // 223-237) with Sinv = I / ell^2:  a = x S x, b = x S u, c = u S u, scale = sqrt(1/a),
 // loc = b/a, Knm = sig2 exp(b^2/(2a) - c/2) sqrt(2 pi) scale (Phi(1) - Phi(0)) |x|, with the
 // normal CDFs of ziggy/misc/stats.py:74-76.  Same formula and rounding steps; |x| = 0 gives
-// NaN exactly where the reference does.
+// NaN exactly where the reference does.  The arithmetic is hgp_kuf_semi.hpp's (semi_sq_*).
 template <typename T>
 __global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_sqexp(KufGrid g, const T* __restrict__ x, int64_t B,
                                                                T sig2, T ell, T* __restrict__ out) {
@@ -142,41 +131,21 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_semi_sqexp(KufGrid g, const
   const int64_t n = rest / outer;
   if (n >= B) return;
   const T sinv = (T)1 / (ell * ell);
-  T xs[3], ua[3];
-  T av = 0, xn2 = 0;
+  T xs[3];
+  const T av = semi_sq_line<T>(x, n, d, sinv, xs);           // xs = xintegrated @ Sinv
   int64_t oi[2] = {0, 0};
   if (d == 2) oi[0] = o;
   if (d == 3) { oi[0] = o / g.m[1]; oi[1] = o % g.m[1]; }
-  for (int ax = 0; ax < d; ++ax) {
-    const T xv = x[n * d + ax];
-    xs[ax] = xv * sinv;                    // xintegrated @ Sinv
-    av += xs[ax] * xv;
-    xn2 += xv * xv;
-    if (ax < d - 1) ua[ax] = reinterpret_cast<const T*>(g.g[ax])[oi[ax]];
-  }
-  T bo = 0, co = 0;                        // outer-axis terms of b and c, in axis order
-  for (int ax = 0; ax < d - 1; ++ax) {
-    bo += xs[ax] * ua[ax];
-    co += (ua[ax] * sinv) * ua[ax];
-  }
-  const T xdist = sqrt(xn2);
+  T bo, co;
+  semi_sq_outer<T>(d, xs, sinv, [&](int ax) -> T { return reinterpret_cast<const T*>(g.g[ax])[oi[ax]]; }, bo, co);
+  const T dist = semi_dist<T>(x, n, d);
   const T scale = sqrt((T)1 / av);
-  const T sqrt2 = (T)1.4142135623730950488, sqrt2pi = (T)2.5066282746310005024;
   const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
   T* orow = out + (n * outer + o) * inner;
 #pragma unroll
   for (int k = 0; k < KUF_PER_THREAD; ++k) {
     const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
-    if (i < inner) {
-      const T ui = gl[i];
-      const T b = (d == 1) ? xs[0] * ui : bo + xs[d - 1] * ui;
-      const T c = (d == 1) ? (ui * sinv) * ui : co + (ui * sinv) * ui;
-      const T loc = b / av;
-      const T coef = sig2 * exp((b * b) / ((T)2 * av) - c / (T)2) * sqrt2pi * scale;
-      const T ca = (T)0.5 * ((T)1 + erf(((T)1 - loc) / (scale * sqrt2)));
-      const T cb = (T)0.5 * ((T)1 + erf(((T)0 - loc) / (scale * sqrt2)));
-      orow[i] = coef * (ca - cb) * xdist;
-    }
+    if (i < inner) orow[i] = semi_sq_elem<T>(d, bo, co, xs[d - 1], gl[i], sinv, av, scale, sig2, dist);
   }
 }
 

@@ -3,9 +3,10 @@
 //   matvec   out[n, s] = sum_{j in window(n)} Kuf[n, j] w[s, j]       (k_kuf_line_win_mv)
 //   rmatvec  out[s, j] = sum_{n: (n, j) in window} c[s, n] Kuf[n, j]   (k_kuf_line_win_rmv)
 // Kuf[n, j] = |x_n| int_0^1 k(u_j, a x_n) da, by the Monte-Carlo mean (MODE 1) or SqExp's closed
-// form (MODE 2), with the bits of k_kuf_semi_mc / k_kuf_semi_sqexp (hgp_kuf_semi.hpp).  The dense
-// twins (k_kuf_semi_mv, k_kuf_semi_rmv) sweep the whole mesh for every line; a line only sees the
-// nodes within the kernel's reach rho of its segment {a x_n : a in [0, 1]}.
+// form (MODE 2), the element that hgp_kuf_semi.hpp defines for the forwards and every product.
+// The dense twins (k_kuf_semi_mv, k_kuf_semi_rmv) sweep the whole mesh for every line; a line only
+// sees the nodes within the kernel's reach rho of its segment {a x_n : a in [0, 1]}.  The host
+// scaffold is hgp_kuf_launch.hpp's.
 //
 // The window.  The segment is cut into P equal pieces, piece p from x (p / P) to x ((p + 1) / P)
 // (lw_end; P = pieces[n] clamped to 1 .. 64, one number per line that both kernels read).  Pair
@@ -30,9 +31,9 @@
 // run, the wave covers the last-axis range.  Per-lane fp64 sums, the xor butterfly, fp64 partials
 // per slice added in slice order (k_kuf_mv_finish).  No atomics.
 //
-// k_kuf_line_win_rmv: a gather.  A block of 256 threads owns a tile of mesh points (256 | 16 x 16 |
-// 4 x 8 x 8, as hgp_kuf_win_bins) and walks ALL lines in chunks of 256: thread t tests line
-// k0 + t against the tile's box (first the whole segment's box, then the pieces, keeping the run
+// k_kuf_line_win_rmv: a gather.  A block owns a tile of mesh points (KufTile, hgp_kuf_tile.hpp: the
+// tiles of hgp_kuf_win_bins), one per thread, and walks ALL lines in chunks of 256: thread t tests
+// line k0 + t against the tile's box (first the whole segment's box, then the pieces, keeping the run
 // of pieces that can reach the tile), the survivors are compacted into LDS in line order by a wave
 // ballot and a prefix over the waves, and every thread applies lw_in and the element function to
 // every survivor.  Products are added in the tensor dtype over a chunk, the chunks in fp64, in
@@ -40,12 +41,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hgp_kuf_launch.hpp"
 #include "hgp_kuf_semi.hpp"
+#include "hgp_kuf_tile.hpp"
 
 namespace hgp {
 
 constexpr int LW_WAVE = 64;         // block of the matvec: one wave
-constexpr int LW_THREADS = 256;     // block of the rmatvec: one tile of mesh points
+constexpr int LW_THREADS = KUF_TILE_THREADS;   // block of the rmatvec: one tile of mesh points
 constexpr int LW_CHUNK = 256;       // lines tested at once (rmatvec); the longest run summed in dtype
 constexpr int LW_MAX_PIECES = 64;   // pieces of a line: one lane each in the matvec
 
@@ -246,35 +249,30 @@ __global__ __launch_bounds__(LW_THREADS) void k_kuf_line_win_rmv(KufGrid g, cons
   __shared__ int pc_s[LW_CHUNK];                              // P | pa << 8 | pb << 16
   __shared__ T al_s[MODE == 1 ? SEMI_MAX_NPTS : 1];           // the Monte-Carlo nodes' alpha
   __shared__ int cnt_s[LW_THREADS / 64];
-  constexpr int T0 = D == 1 ? 256 : (D == 2 ? 16 : 4);        // the tiles of hgp_kuf_win_bins
-  constexpr int T1 = D == 1 ? 1 : (D == 2 ? 16 : 8);
-  constexpr int T2 = D == 3 ? 8 : 1;
+  constexpr int T0 = KufTile<D>::T0, T1 = KufTile<D>::T1, T2 = KufTile<D>::T2;
   const int d = g.d;                                          // = D; an argument, not a constant, for the
   const int tid = threadIdx.x;                                // axis loops of hgp_kuf_semi.hpp
   const int lane = tid & 63, wv = tid >> 6;
-  const int64_t m0 = g.m[0], m1 = D > 1 ? g.m[1] : 1, m2 = D > 2 ? g.m[2] : 1;
+  // the block's tile and the thread's mesh point in it
+  const KufTilePos tp = kuf_tile_pos<D>(g);
+  const int64_t m0 = tp.m0, m1 = tp.m1, m2 = tp.m2, i0 = tp.i0, i1 = tp.i1, i2 = tp.i2;
+  const bool live = tp.live;
   const T* g0 = reinterpret_cast<const T*>(g.g[0]);
   const T* g1 = reinterpret_cast<const T*>(g.g[D > 1 ? 1 : 0]);
   const T* g2 = reinterpret_cast<const T*>(g.g[D > 2 ? 2 : 0]);
-  // the block's tile (C order over the tiles of the axes) and the thread's mesh point in it
-  const int64_t nt1 = (m1 + T1 - 1) / T1, nt2 = (m2 + T2 - 1) / T2;
-  const int64_t bt = blockIdx.x;
-  const int64_t t0 = bt / (nt1 * nt2), t1 = (bt / nt2) % nt1, t2 = bt % nt2;
-  const int64_t i0 = t0 * T0 + tid / (T1 * T2), i1 = t1 * T1 + (tid / T2) % T1, i2 = t2 * T2 + tid % T2;
-  const bool live = i0 < m0 && i1 < m1 && i2 < m2;
   T uv[3] = {0, 0, 0}, tlo[3] = {0, 0, 0}, thi[3] = {0, 0, 0};
   uv[0] = g0[i0 < m0 ? i0 : m0 - 1];
-  tlo[0] = g0[t0 * T0];
-  thi[0] = g0[t0 * T0 + T0 - 1 < m0 ? t0 * T0 + T0 - 1 : m0 - 1];
+  tlo[0] = g0[tp.t0 * T0];
+  thi[0] = g0[tp.t0 * T0 + T0 - 1 < m0 ? tp.t0 * T0 + T0 - 1 : m0 - 1];
   if (D > 1) {
     uv[1] = g1[i1 < m1 ? i1 : m1 - 1];
-    tlo[1] = g1[t1 * T1];
-    thi[1] = g1[t1 * T1 + T1 - 1 < m1 ? t1 * T1 + T1 - 1 : m1 - 1];
+    tlo[1] = g1[tp.t1 * T1];
+    thi[1] = g1[tp.t1 * T1 + T1 - 1 < m1 ? tp.t1 * T1 + T1 - 1 : m1 - 1];
   }
   if (D > 2) {
     uv[2] = g2[i2 < m2 ? i2 : m2 - 1];
-    tlo[2] = g2[t2 * T2];
-    thi[2] = g2[t2 * T2 + T2 - 1 < m2 ? t2 * T2 + T2 - 1 : m2 - 1];
+    tlo[2] = g2[tp.t2 * T2];
+    thi[2] = g2[tp.t2 * T2 + T2 - 1 < m2 ? tp.t2 * T2 + T2 - 1 : m2 - 1];
   }
   const bool sq = scaled_dist(kind);
   const T sinv = (T)1 / (ell * ell);
@@ -376,71 +374,10 @@ __global__ __launch_bounds__(LW_THREADS) void k_kuf_line_win_rmv(KufGrid g, cons
     }
   }
   if (!live) return;
-  const int64_t j = (D == 1 ? i0 : (D == 2 ? i0 * m1 + i1 : (i0 * m1 + i1) * m2 + i2));
+  const int64_t j = tp.flat<D>();
 #pragma unroll
   for (int s = 0; s < NC; ++s)
     if (s < ncv) out[(int64_t)s * M + j] = (T)acc[s];
-}
-
-static int lw_cus(hipError_t* e) {
-  static int cus[64] = {0};
-  int dev = 0;
-  *e = hipGetDevice(&dev);
-  if (*e != hipSuccess) return 0;
-  if (dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int v = 0;
-    *e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    if (*e != hipSuccess) return 0;
-    cus[dev] = v > 0 ? v : 256;
-  }
-  return cus[dev];
-}
-
-// the width of the next group of weight / coefficient rows, as the dense products
-static inline int lw_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
-
-template <typename T, int MODE>
-static void launch_lw_mv(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, int kind, T sig2,
-                         T ell, T kp, T rho, int npts, const T* u, const int* pieces, const T* w, int nwv, int64_t M,
-                         int nsplit, double* part, T* out, int64_t ldo) {
-  if (NW == 8)
-    hipLaunchKernelGGL((k_kuf_line_win_mv<T, MODE, 8>), dim3(nb), dim3(LW_WAVE), 0, s, g, x, B, kind, sig2, ell, kp,
-                       rho, npts, u, pieces, w, nwv, M, nsplit, part, out, ldo);
-  else if (NW == 4)
-    hipLaunchKernelGGL((k_kuf_line_win_mv<T, MODE, 4>), dim3(nb), dim3(LW_WAVE), 0, s, g, x, B, kind, sig2, ell, kp,
-                       rho, npts, u, pieces, w, nwv, M, nsplit, part, out, ldo);
-  else
-    hipLaunchKernelGGL((k_kuf_line_win_mv<T, MODE, 1>), dim3(nb), dim3(LW_WAVE), 0, s, g, x, B, kind, sig2, ell, kp,
-                       rho, npts, u, pieces, w, nwv, M, nsplit, part, out, ldo);
-}
-
-template <typename T, int MODE, int D>
-static void launch_lw_rmv_d(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, int kind,
-                            T sig2, T ell, T kp, T rho, int npts, const T* u, const int* pieces, const T* c, int ncv,
-                            int64_t M, T* out) {
-  if (NC == 8)
-    hipLaunchKernelGGL((k_kuf_line_win_rmv<T, MODE, 8, D>), dim3(nb), dim3(LW_THREADS), 0, s, g, x, B, kind, sig2, ell,
-                       kp, rho, npts, u, pieces, c, ncv, M, out);
-  else if (NC == 4)
-    hipLaunchKernelGGL((k_kuf_line_win_rmv<T, MODE, 4, D>), dim3(nb), dim3(LW_THREADS), 0, s, g, x, B, kind, sig2, ell,
-                       kp, rho, npts, u, pieces, c, ncv, M, out);
-  else
-    hipLaunchKernelGGL((k_kuf_line_win_rmv<T, MODE, 1, D>), dim3(nb), dim3(LW_THREADS), 0, s, g, x, B, kind, sig2, ell,
-                       kp, rho, npts, u, pieces, c, ncv, M, out);
-}
-
-static int64_t lw_grid(KufGrid& g, int ndim, const int64_t* m, const void* const* grids, int64_t* outer) {
-  g.d = ndim;
-  int64_t M = 1;
-  *outer = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    M *= m[a];
-    if (a < ndim - 1) *outer *= m[a];
-  }
-  return M;
 }
 
 // mode 1: semi-mc, 2: semi-sqexp.  nobs > 0, nw > 0
@@ -450,8 +387,8 @@ static hipError_t kuf_line_matvec_win_t(int mode, int kind, double kp, int ndim,
                                         double ell, double rho, int npts, const void* uv, const int* pieces,
                                         const void* wv, int64_t nw, void* outv, hipStream_t s) {
   KufGrid g{};
-  int64_t outer = 1;
-  const int64_t M = lw_grid(g, ndim, m, grids, &outer);
+  int64_t M, outer;
+  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
   const T* x = reinterpret_cast<const T*>(xv);
   const T* w = reinterpret_cast<const T*>(wv);
   const T* u = reinterpret_cast<const T*>(uv);
@@ -459,43 +396,29 @@ static hipError_t kuf_line_matvec_win_t(int mode, int kind, double kp, int ndim,
   // the split: a pure function of (nobs, the grid) and the CU count; a slice is a share of the rows
   // of the line's own outer bounding range
   hipError_t e = hipSuccess;
-  const int64_t target = (int64_t)16 * lw_cus(&e);
+  const int64_t target = (int64_t)16 * kuf_cus(&e);
   if (e != hipSuccess) return e;
   int64_t nsplit = (target + nobs - 1) / nobs;
   if (nsplit > outer) nsplit = outer;
   if (nsplit < 1) nsplit = 1;
   if (nobs * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)(nobs * nsplit);
-  double* part = nullptr;
-  if (nsplit > 1) {
-    e = hipMallocAsync(reinterpret_cast<void**>(&part),
-                       (size_t)nsplit * (size_t)nobs * (size_t)lw_group(nw) * sizeof(double), s);
-    if (e != hipSuccess) return e;
-  }
-  for (int64_t s0 = 0; s0 < nw;) {
-    const int NW = lw_group(nw - s0);
-    const int nwv = (int)(nw - s0 < NW ? nw - s0 : NW);
-    const T* wg = w + s0 * M;
-    T* og = out + s0;
-    if (mode == 1)
-      launch_lw_mv<T, 1>(NW, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces, wg, nwv, M,
-                         (int)nsplit, part, og, nw);
-    else
-      launch_lw_mv<T, 2>(NW, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces, wg, nwv, M,
-                         (int)nsplit, part, og, nw);
-    if (part != nullptr) {
-      const int64_t tot = nobs * NW;
-      hipLaunchKernelGGL((k_kuf_mv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
-                         (int)nsplit, nobs, NW, nwv, og, nw);
-    }
-    s0 += nwv;
-  }
-  e = hipGetLastError();
-  if (part != nullptr) {
-    const hipError_t f = hipFreeAsync(part, s);
-    if (e == hipSuccess) e = f;
-  }
-  return e;
+  return kuf_row_groups(
+      nw, nsplit > 1 ? (size_t)nsplit * (size_t)nobs : 0, s,
+      [&](int64_t s0, int NW, int nwv, double* part) {
+        kuf_with_mode(mode, [&](auto MD) {
+          kuf_with_width(NW, [&](auto W) {
+            hipLaunchKernelGGL((k_kuf_line_win_mv<T, decltype(MD)::value, decltype(W)::value>), dim3(nb),
+                               dim3(LW_WAVE), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces,
+                               w + s0 * M, nwv, M, (int)nsplit, part, out + s0, nw);
+          });
+        });
+      },
+      [&](int64_t s0, int NW, int nwv, double* part) {
+        const int64_t tot = nobs * NW;
+        hipLaunchKernelGGL((k_kuf_mv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
+                           (int)nsplit, nobs, NW, nwv, out + s0, nw);
+      });
 }
 
 // nobs >= 0 (0: out zeroed), nc > 0
@@ -505,41 +428,28 @@ static hipError_t kuf_line_rmatvec_win_t(int mode, int kind, double kp, int ndim
                                          double ell, double rho, int npts, const void* uv, const int* pieces,
                                          const void* cv, int64_t nc, void* outv, hipStream_t s) {
   KufGrid g{};
-  int64_t outer = 1;
-  const int64_t M = lw_grid(g, ndim, m, grids, &outer);
+  int64_t M, outer;
+  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
   T* out = reinterpret_cast<T*>(outv);
   if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
   const T* x = reinterpret_cast<const T*>(xv);
   const T* c = reinterpret_cast<const T*>(cv);
   const T* u = reinterpret_cast<const T*>(uv);
-  int64_t ntile = 1;
-  for (int a = 0; a < ndim; ++a) {
-    const int64_t t = ndim == 1 ? 256 : (ndim == 2 ? 16 : (a == 0 ? 4 : 8));
-    ntile *= (m[a] + t - 1) / t;
-  }
+  const int64_t ntile = kuf_tile_count(ndim, m);
   if (ntile > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)ntile;
-  for (int64_t s0 = 0; s0 < nc;) {
-    const int NC = lw_group(nc - s0);
-    const int ncv = (int)(nc - s0 < NC ? nc - s0 : NC);
-    const T* cg = c + s0 * nobs;
-    T* og = out + s0 * M;
-#define HGP_LW_RMV(MODE, D)                                                                                          \
-  launch_lw_rmv_d<T, MODE, D>(NC, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces, cg, ncv, \
-                              M, og)
-    if (mode == 1) {
-      if (ndim == 1) HGP_LW_RMV(1, 1);
-      else if (ndim == 2) HGP_LW_RMV(1, 2);
-      else HGP_LW_RMV(1, 3);
-    } else {
-      if (ndim == 1) HGP_LW_RMV(2, 1);
-      else if (ndim == 2) HGP_LW_RMV(2, 2);
-      else HGP_LW_RMV(2, 3);
-    }
-#undef HGP_LW_RMV
-    s0 += ncv;
-  }
-  return hipGetLastError();
+  return kuf_row_groups(nc, s, [&](int64_t s0, int NC, int ncv, double*) {
+    kuf_with_mode(mode, [&](auto MD) {
+      kuf_with_dim(ndim, [&](auto D) {
+        kuf_with_width(NC, [&](auto W) {
+          hipLaunchKernelGGL(
+              (k_kuf_line_win_rmv<T, decltype(MD)::value, decltype(W)::value, decltype(D)::value>), dim3(nb),
+              dim3(LW_THREADS), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces,
+              c + s0 * nobs, ncv, M, out + s0 * M);
+        });
+      });
+    });
+  });
 }
 
 // launcher behind hgp_kuf_semi_mc_matvec_win / hgp_kuf_semi_sqexp_matvec_win

@@ -3,7 +3,8 @@
 // With w = K^-1 R qm this is the posterior mean at nobs points from ONE solve (the reference
 // solves once per point: hipgp.py:416-446 through svi_gp.py:72 and hipgp.py:117-146); with
 // several weight rows, joint draws of the projected process.  The element values come from the
-// same device functions as the forwards (hgp_kuf_eval.hpp).
+// same device functions as the forwards (hgp_kuf_eval.hpp; line integrals: hgp_kuf_semi.hpp), the
+// host scaffold (CU count, row groups, partials, the kind / width ladders) from hgp_kuf_launch.hpp.
 //
 // Point observations (k_kuf_grid_mv), the hot path: compute bound, nobs * M kernel values each
 // used nw times.  A block is ONE wave and owns a tile of 64 points, one per lane: the lane's
@@ -26,6 +27,7 @@
 #include <stdint.h>
 
 #include "hgp_kuf_eval.hpp"
+#include "hgp_kuf_launch.hpp"
 #include "hgp_kuf_semi.hpp"
 
 namespace hgp {
@@ -188,68 +190,14 @@ __global__ __launch_bounds__(MV_THREADS) void k_kuf_semi_mv(KufGrid g, const T* 
   }
 }
 
-static int mv_cus(hipError_t* e) {
-  static int cus[64] = {0};
-  int dev = 0;
-  *e = hipGetDevice(&dev);
-  if (*e != hipSuccess) return 0;
-  if (dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int v = 0;
-    *e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    if (*e != hipSuccess) return 0;
-    cus[dev] = v > 0 ? v : 256;
-  }
-  return cus[dev];
-}
-
-// the width of the next group of weight rows
-static inline int mv_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
-
-template <typename T, int KIND>
-static void launch_grid_mv(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2, T ell,
-                           const T* w, int nwv, int64_t M, int nsplit, int64_t nunit, double* part, T* out,
-                           int64_t ldo) {
-  if (NW == 8)
-    hipLaunchKernelGGL((k_kuf_grid_mv<T, KIND, 8>), dim3(nb), dim3(MV_TILE), 0, s, g, x, B, sig2, ell, w, nwv, M,
-                       nsplit, nunit, part, out, ldo);
-  else if (NW == 4)
-    hipLaunchKernelGGL((k_kuf_grid_mv<T, KIND, 4>), dim3(nb), dim3(MV_TILE), 0, s, g, x, B, sig2, ell, w, nwv, M,
-                       nsplit, nunit, part, out, ldo);
-  else
-    hipLaunchKernelGGL((k_kuf_grid_mv<T, KIND, 1>), dim3(nb), dim3(MV_TILE), 0, s, g, x, B, sig2, ell, w, nwv, M,
-                       nsplit, nunit, part, out, ldo);
-}
-
-template <typename T, int MODE>
-static void launch_semi_mv(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, int kind,
-                           T sig2, T ell, T kp, int npts, const T* u, const T* w, int nwv, int64_t M, int nsplit,
-                           double* part, T* out, int64_t ldo) {
-  if (NW == 8)
-    hipLaunchKernelGGL((k_kuf_semi_mv<T, MODE, 8>), dim3(nb), dim3(MV_THREADS), 0, s, g, x, B, kind, sig2, ell, kp,
-                       npts, u, w, nwv, M, nsplit, part, out, ldo);
-  else if (NW == 4)
-    hipLaunchKernelGGL((k_kuf_semi_mv<T, MODE, 4>), dim3(nb), dim3(MV_THREADS), 0, s, g, x, B, kind, sig2, ell, kp,
-                       npts, u, w, nwv, M, nsplit, part, out, ldo);
-  else
-    hipLaunchKernelGGL((k_kuf_semi_mv<T, MODE, 1>), dim3(nb), dim3(MV_THREADS), 0, s, g, x, B, kind, sig2, ell, kp,
-                       npts, u, w, nwv, M, nsplit, part, out, ldo);
-}
-
 // mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs > 0, nw > 0, nsplit >= 0.
 template <typename T>
 static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
                                const void* xv, int64_t nobs, double sig2, double ell, int npts, const void* uv,
                                const void* wv, int64_t nw, int64_t nsplit_in, void* outv, hipStream_t s) {
   KufGrid g{};
-  g.d = ndim;
-  int64_t outer = 1, M = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    M *= m[a];
-    if (a < ndim - 1) outer *= m[a];
-  }
+  int64_t M, outer;
+  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
   const T* x = reinterpret_cast<const T*>(xv);
   const T* w = reinterpret_cast<const T*>(wv);
   const T* u = reinterpret_cast<const T*>(uv);
@@ -260,7 +208,7 @@ static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const in
   int64_t nsplit = nsplit_in;
   if (nsplit == 0) {
     hipError_t e = hipSuccess;
-    const int64_t target = (int64_t)(mode == 0 ? 16 : 4) * mv_cus(&e);          // blocks that fill the device
+    const int64_t target = (int64_t)(mode == 0 ? 16 : 4) * kuf_cus(&e);         // blocks that fill the device
     if (e != hipSuccess) return e;
     const int64_t most = mode == 0 ? nunit / MV_MIN_UNITS : nunit;
     nsplit = (target + nrow - 1) / nrow;
@@ -270,55 +218,30 @@ static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const in
   if (nsplit > nunit) nsplit = nunit;
   if (nrow * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)(nrow * nsplit);
-  double* part = nullptr;
-  if (nsplit > 1) {
-    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part),
-                                  (size_t)nsplit * (size_t)nobs * (size_t)mv_group(nw) * sizeof(double), s);
-    if (e != hipSuccess) return e;
-  }
-  for (int64_t s0 = 0; s0 < nw;) {
-    const int NW = mv_group(nw - s0);
-    const int nwv = (int)(nw - s0 < NW ? nw - s0 : NW);
-    const T* wg = w + s0 * M;
-    T* og = out + s0;
-    if (mode == 0) {
-      switch (kind) {
-        case HGP_KERN_SQEXP:
-          launch_grid_mv<T, HGP_KERN_SQEXP>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
-                                            part, og, nw);
-          break;
-        case HGP_KERN_MATERN12:
-          launch_grid_mv<T, HGP_KERN_MATERN12>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
-                                               part, og, nw);
-          break;
-        case HGP_KERN_MATERN32:
-          launch_grid_mv<T, HGP_KERN_MATERN32>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
-                                               part, og, nw);
-          break;
-        default:
-          launch_grid_mv<T, HGP_KERN_MATERN52>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit,
-                                               part, og, nw);
-      }
-    } else if (mode == 1) {
-      launch_semi_mv<T, 1>(NW, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, wg, nwv, M, (int)nsplit, part,
-                           og, nw);
-    } else {
-      launch_semi_mv<T, 2>(NW, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, wg, nwv, M, (int)nsplit, part,
-                           og, nw);
-    }
-    if (part != nullptr) {
-      const int64_t tot = nobs * NW;
-      hipLaunchKernelGGL((k_kuf_mv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
-                         (int)nsplit, nobs, NW, nwv, og, nw);
-    }
-    s0 += nwv;
-  }
-  hipError_t e = hipGetLastError();
-  if (part != nullptr) {
-    const hipError_t f = hipFreeAsync(part, s);
-    if (e == hipSuccess) e = f;
-  }
-  return e;
+  return kuf_row_groups(
+      nw, nsplit > 1 ? (size_t)nsplit * (size_t)nobs : 0, s,
+      [&](int64_t s0, int NW, int nwv, double* part) {
+        const T* wg = w + s0 * M;
+        T* og = out + s0;
+        kuf_with_width(NW, [&](auto W) {
+          if (mode == 0)
+            kuf_with_kind(kind, [&](auto K) {
+              hipLaunchKernelGGL((k_kuf_grid_mv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(MV_TILE),
+                                 0, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit, part, og, nw);
+            });
+          else
+            kuf_with_mode(mode, [&](auto MD) {
+              hipLaunchKernelGGL((k_kuf_semi_mv<T, decltype(MD)::value, decltype(W)::value>), dim3(nb),
+                                 dim3(MV_THREADS), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, wg, nwv, M,
+                                 (int)nsplit, part, og, nw);
+            });
+        });
+      },
+      [&](int64_t s0, int NW, int nwv, double* part) {
+        const int64_t tot = nobs * NW;
+        hipLaunchKernelGGL((k_kuf_mv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
+                           (int)nsplit, nobs, NW, nwv, out + s0, nw);
+      });
 }
 
 // launcher behind hgp_kuf_grid_matvec / hgp_kuf_semi_mc_matvec / hgp_kuf_semi_sqexp_matvec

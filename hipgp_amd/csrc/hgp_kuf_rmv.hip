@@ -4,7 +4,8 @@
 //   (K + Kuf^T diag(iv) Kuf) beta = Kuf^T (iv o y)
 // runs matrix-free, which is the optimal variational mean of all observations at once
 // (`ToeplitzInducingGP.fit_mean`).  Element values come from the same device functions as the
-// forwards (hgp_kuf_eval.hpp).
+// forwards (hgp_kuf_eval.hpp; line integrals: hgp_kuf_semi.hpp), the host scaffold from
+// hgp_kuf_launch.hpp.
 //
 // Point observations (k_kuf_grid_rmv), the hot path: compute bound, nobs * M kernel values each
 // used nc times.  The roles of k_kuf_grid_mv turned round: a block is ONE wave and owns a tile of
@@ -29,49 +30,26 @@
 #include <stdint.h>
 
 #include "hgp_kuf_eval.hpp"
+#include "hgp_kuf_launch.hpp"
+#include "hgp_kuf_semi.hpp"
 
 namespace hgp {
 
 constexpr int RMV_TILE = 64;      // mesh points per block (one wave), both kernels
 constexpr int RMV_RUN = 256;      // longest run summed in the tensor dtype; the unit of the split
 
-__device__ __forceinline__ float rmv_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double rmv_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-// The squared distance of k_kuf_grid with its roundings spelled out.  There the outer axes' sum is
-// a block constant formed ahead of the last-axis term, and hipcc contracts what is left in one
-// way only: so = dv0^2 (2-D) or fma(dv0, dv0, dv1^2) (3-D), s = fma(dvl, dvl, so), s = dvl^2 (1-D).
-// Here all three products meet in one expression, where contraction could pair them differently
-// (SqExp at s = 60 turns one ulp of s into 4e-6 of the value), so it is switched off and the
-// forward's pairing is written with explicit fused multiply-adds.
-template <typename T, int D>
-__device__ __forceinline__ T rmv_sqdist(T d0, T d1, T dl) {
-#pragma clang fp contract(off)
-  if (D == 1) return dl * dl;
-  if (D == 2) return rmv_fma(dl, dl, d0 * d0);
-  return rmv_fma(dl, dl, rmv_fma(d0, d0, d1 * d1));
-}
-
 // One run [r0, r1) of observations for the lane's mesh point (u0, u1, ul): run[s] += Kuf * c.
-// D is the number of axes.
+// D is the number of axes.  All three axes' products meet in one expression here, so the squared
+// distance is kuf_sqdist's, with the forward's roundings spelled out.
 template <typename T, int KIND, int NC, int D>
 __device__ __forceinline__ void rmv_run(const T* __restrict__ x, int64_t r0, int64_t r1, T u0, T u1, T ul, T sig2,
                                         T ell, const T* const (&cp)[NC], T (&run)[NC]) {
-  constexpr bool sq = KIND == HGP_KERN_SQEXP || KIND == HGP_KERN_GNEITING;
 #pragma unroll 4
   for (int64_t n = r0; n < r1; ++n) {
-    T d0 = 0, d1 = 0;
-    if (D >= 2) {
-      d0 = x[n * D] - u0;
-      if (sq) d0 = d0 / ell;
-    }
-    if (D == 3) {
-      d1 = x[n * D + 1] - u1;
-      if (sq) d1 = d1 / ell;
-    }
-    T dv = x[n * D + D - 1] - ul;
-    if (sq) dv = dv / ell;
-    const T sv = rmv_sqdist<T, D>(d0, d1, dv);
+    const T d0 = D >= 2 ? kuf_axis<T, KIND>(x[n * D], u0, ell) : (T)0;
+    const T d1 = D == 3 ? kuf_axis<T, KIND>(x[n * D + 1], u1, ell) : (T)0;
+    const T dv = kuf_axis<T, KIND>(x[n * D + D - 1], ul, ell);
+    const T sv = kuf_sqdist<T>(D, d0, d1, dv);
     const T kv = kern_eval<T>(KIND, sv, sig2, ell);
 #pragma unroll
     for (int s = 0; s < NC; ++s) run[s] += kv * cp[s][n];
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(256) void k_kuf_rmv_finish(const double* __restrict
 
 // MODE 1: the Monte-Carlo line integral of k_kuf_semi_mc; MODE 2: the analytic SqExp one of
 // k_kuf_semi_sqexp.  Block (outer index o, 64 points of the last axis, slice of the observations);
-// element values formed as the forwards do.
+// element values by hgp_kuf_semi.hpp (MODE 1; MODE 2 see below).
 template <typename T, int MODE, int NC>
 __global__ __launch_bounds__(RMV_TILE) void k_kuf_semi_rmv(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
                                                           T sig2, T ell, T kp, int npts, const T* __restrict__ u,
@@ -178,38 +156,30 @@ __global__ __launch_bounds__(RMV_TILE) void k_kuf_semi_rmv(KufGrid g, const T* _
 
   if (MODE == 1) {
     const bool sq = scaled_dist(kind);
-    const T uoff = u[0] * (T)(1.0 / (double)npts);
+    const T uoff = semi_mc_offset<T>(u, npts);
     for (int64_t n = n0; n < n1; ++n) {                       // the same trip count for every lane
       __syncthreads();                                        // the last observation's readers are done
       for (int a = threadIdx.x; a < npts; a += RMV_TILE) {
-        const T al = (T)a / (T)npts + uoff;
-        auto sqd = [&](int ax, int64_t ia) -> T {
-          T dv = reinterpret_cast<const T*>(g.g[ax])[ia] - x[n * d + ax] * al;
-          if (sq) dv = dv / ell;
-          return dv * dv;
-        };
-        T so = 0;
-        if (d == 2) so = sqd(0, o);
-        if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
-        so_s[a] = so;
+        const T al = semi_mc_alpha<T>(a, npts, uoff);
+        so_s[a] = semi_mc_outer<T>(d, [&](int ax) -> T {
+          const int64_t ia = d == 2 ? o : (ax == 0 ? o / g.m[1] : o % g.m[1]);
+          return semi_mc_sqd<T>(reinterpret_cast<const T*>(g.g[ax])[ia], x[n * d + ax], al, sq, ell);
+        });
         xl_s[a] = x[n * d + d - 1] * al;
       }
       __syncthreads();
-      T xn2 = 0;
-      for (int ax = 0; ax < d; ++ax) xn2 += x[n * d + ax] * x[n * d + ax];
-      const T dist = sqrt(xn2);
-      T ka = 0;
-      for (int a = 0; a < npts; ++a) {
-        T dv = ui - xl_s[a];
-        if (sq) dv = dv / ell;
-        const T sv = (d == 1) ? dv * dv : so_s[a] + dv * dv;
-        ka += kern_eval<T>(kind, sv, sig2, ell, kp);
-      }
-      const T kv = ka / (T)npts * dist;
+      const T dist = semi_dist<T>(x, n, d);
+      const T kv = semi_mc_elem<T>(kind, d, ui, npts, sq, sig2, ell, kp, dist, [&](int a, T& xl, T& so) {
+        xl = xl_s[a];
+        so = so_s[a];
+      });
 #pragma unroll
       for (int s = 0; s < NC; ++s) acc[s] += (double)(kv * cp[s][n]);
     }
   } else {
+    // This branch keeps its own spelling of the analytic form.  Here the product (ui sinv) ui feeds
+    // both arms of the d == 1 choice, so hipcc leaves c = co + (ui sinv) ui as a product and a sum,
+    // where semi_sq_elem fuses them: from two axes on the bits would differ in c's last place.
     const T sinv = (T)1 / (ell * ell);
     const T sqrt2 = (T)1.4142135623730950488, sqrt2pi = (T)2.5066282746310005024;
     int64_t oi[2] = {0, 0};
@@ -257,67 +227,14 @@ __global__ __launch_bounds__(RMV_TILE) void k_kuf_semi_rmv(KufGrid g, const T* _
   }
 }
 
-static int rmv_cus(hipError_t* e) {
-  static int cus[64] = {0};
-  int dev = 0;
-  *e = hipGetDevice(&dev);
-  if (*e != hipSuccess) return 0;
-  if (dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int v = 0;
-    *e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    if (*e != hipSuccess) return 0;
-    cus[dev] = v > 0 ? v : 256;
-  }
-  return cus[dev];
-}
-
-// the width of the next group of coefficient rows
-static inline int rmv_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
-
-template <typename T, int KIND>
-static void launch_grid_rmv(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2,
-                            T ell, const T* c, int ncv, int64_t M, int nsplit, int64_t nrun, double* part, T* out) {
-  if (NC == 8)
-    hipLaunchKernelGGL((k_kuf_grid_rmv<T, KIND, 8>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, sig2, ell, c, ncv, M,
-                       nsplit, nrun, part, out);
-  else if (NC == 4)
-    hipLaunchKernelGGL((k_kuf_grid_rmv<T, KIND, 4>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, sig2, ell, c, ncv, M,
-                       nsplit, nrun, part, out);
-  else
-    hipLaunchKernelGGL((k_kuf_grid_rmv<T, KIND, 1>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, sig2, ell, c, ncv, M,
-                       nsplit, nrun, part, out);
-}
-
-template <typename T, int MODE>
-static void launch_semi_rmv(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, int kind,
-                            T sig2, T ell, T kp, int npts, const T* u, const T* c, int ncv, int64_t M, int nsplit,
-                            int64_t nrun, int64_t nchunk, double* part, T* out) {
-  if (NC == 8)
-    hipLaunchKernelGGL((k_kuf_semi_rmv<T, MODE, 8>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, kind, sig2, ell, kp,
-                       npts, u, c, ncv, M, nsplit, nrun, nchunk, part, out);
-  else if (NC == 4)
-    hipLaunchKernelGGL((k_kuf_semi_rmv<T, MODE, 4>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, kind, sig2, ell, kp,
-                       npts, u, c, ncv, M, nsplit, nrun, nchunk, part, out);
-  else
-    hipLaunchKernelGGL((k_kuf_semi_rmv<T, MODE, 1>), dim3(nb), dim3(RMV_TILE), 0, s, g, x, B, kind, sig2, ell, kp,
-                       npts, u, c, ncv, M, nsplit, nrun, nchunk, part, out);
-}
-
 // mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs >= 0, nc > 0, nsplit >= 0.
 template <typename T>
 static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
                                 const void* xv, int64_t nobs, double sig2, double ell, int npts, const void* uv,
                                 const void* cv, int64_t nc, int64_t nsplit_in, void* outv, hipStream_t s) {
   KufGrid g{};
-  g.d = ndim;
-  int64_t outer = 1, M = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    M *= m[a];
-    if (a < ndim - 1) outer *= m[a];
-  }
+  int64_t M, outer;
+  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
   T* out = reinterpret_cast<T*>(outv);
   if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
   const T* x = reinterpret_cast<const T*>(xv);
@@ -331,62 +248,37 @@ static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const i
   int64_t nsplit = nsplit_in;
   if (nsplit == 0) {
     hipError_t e = hipSuccess;
-    const int64_t target = (int64_t)16 * rmv_cus(&e);        // one-wave blocks that fill the device
+    const int64_t target = (int64_t)16 * kuf_cus(&e);        // one-wave blocks that fill the device
     if (e != hipSuccess) return e;
     nsplit = ntile >= target ? 1 : (target + ntile - 1) / ntile;
   }
   if (nsplit > nrun) nsplit = nrun;
   if (ntile * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)(ntile * nsplit);
-  double* part = nullptr;
-  if (nsplit > 1) {
-    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part),
-                                  (size_t)nsplit * (size_t)rmv_group(nc) * (size_t)M * sizeof(double), s);
-    if (e != hipSuccess) return e;
-  }
-  for (int64_t s0 = 0; s0 < nc;) {
-    const int NC = rmv_group(nc - s0);
-    const int ncv = (int)(nc - s0 < NC ? nc - s0 : NC);
-    const T* cg = c + s0 * nobs;
-    T* og = out + s0 * M;
-    if (mode == 0) {
-      switch (kind) {
-        case HGP_KERN_SQEXP:
-          launch_grid_rmv<T, HGP_KERN_SQEXP>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
-                                             part, og);
-          break;
-        case HGP_KERN_MATERN12:
-          launch_grid_rmv<T, HGP_KERN_MATERN12>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
-                                                part, og);
-          break;
-        case HGP_KERN_MATERN32:
-          launch_grid_rmv<T, HGP_KERN_MATERN32>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
-                                                part, og);
-          break;
-        default:
-          launch_grid_rmv<T, HGP_KERN_MATERN52>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun,
-                                                part, og);
-      }
-    } else if (mode == 1) {
-      launch_semi_rmv<T, 1>(NC, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, cg, ncv, M, (int)nsplit,
-                            nrun, nchunk, part, og);
-    } else {
-      launch_semi_rmv<T, 2>(NC, nb, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, cg, ncv, M, (int)nsplit,
-                            nrun, nchunk, part, og);
-    }
-    if (part != nullptr) {
-      const int64_t tot = M * ncv;
-      hipLaunchKernelGGL((k_kuf_rmv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
-                         (int)nsplit, M, NC, ncv, og);
-    }
-    s0 += ncv;
-  }
-  hipError_t e = hipGetLastError();
-  if (part != nullptr) {
-    const hipError_t f = hipFreeAsync(part, s);
-    if (e == hipSuccess) e = f;
-  }
-  return e;
+  return kuf_row_groups(
+      nc, nsplit > 1 ? (size_t)nsplit * (size_t)M : 0, s,
+      [&](int64_t s0, int NC, int ncv, double* part) {
+        const T* cg = c + s0 * nobs;
+        T* og = out + s0 * M;
+        kuf_with_width(NC, [&](auto W) {
+          if (mode == 0)
+            kuf_with_kind(kind, [&](auto K) {
+              hipLaunchKernelGGL((k_kuf_grid_rmv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(RMV_TILE),
+                                 0, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun, part, og);
+            });
+          else
+            kuf_with_mode(mode, [&](auto MD) {
+              hipLaunchKernelGGL((k_kuf_semi_rmv<T, decltype(MD)::value, decltype(W)::value>), dim3(nb),
+                                 dim3(RMV_TILE), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, cg, ncv, M,
+                                 (int)nsplit, nrun, nchunk, part, og);
+            });
+        });
+      },
+      [&](int64_t s0, int NC, int ncv, double* part) {
+        const int64_t tot = M * ncv;
+        hipLaunchKernelGGL((k_kuf_rmv_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part,
+                           (int)nsplit, M, NC, ncv, out + s0 * M);
+      });
 }
 
 // launcher behind hgp_kuf_grid_rmatvec / hgp_kuf_semi_mc_rmatvec / hgp_kuf_semi_sqexp_rmatvec

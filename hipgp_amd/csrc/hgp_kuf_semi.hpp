@@ -1,13 +1,15 @@
-// hgp_kuf_semi.hpp — the per-element arithmetic of the line-integral cross covariances as the
-// products form it, shared by the dense product (k_kuf_semi_mv, hgp_kuf_mv.hip) and the windowed
-// ones (hgp_kuf_line_win.hip) so that an element has the same bits in all of them: the operations
-// and their order are those of k_kuf_semi_mc / k_kuf_semi_sqexp (hgp_kuf.hip).
+// hgp_kuf_semi.hpp — the element of the line-integral cross covariances, Kuf[n, j] = |x_n| *
+// int_0^1 k(u_j, a x_n) da by the Monte-Carlo mean (semi_mc_*) or SqExp's closed form (semi_sq_*):
+// its one definition, operations and their order.  The forwards (k_kuf_semi_mc, k_kuf_semi_sqexp:
+// hgp_kuf.hip), the dense products (k_kuf_semi_mv, k_kuf_semi_rmv) and the windowed ones
+// (hgp_kuf_line_win.hip) all form it through these functions, so it has the same bits in all.
 //
 // hipcc contracts a product and a sum into one fused multiply-add where both meet in one basic
-// block.  The forwards and the dense product form the per-row terms (so, xl of a Monte-Carlo node;
-// bo, co of the analytic form) ahead of the last-axis loop, so there they arrive as finished,
-// rounded values.  A kernel that forms them next to the element itself passes them through
-// semi_rounded first: the compiler then sees a finished value too, and pairs the same operations.
+// block.  The forwards and the dense products form the per-row terms (so, xl of a Monte-Carlo
+// node; bo, co of the analytic form) ahead of the element, in LDS or ahead of the last-axis loop,
+// so there they arrive as finished, rounded values.  A kernel that forms them next to the element
+// itself passes them through semi_rounded first: the compiler then sees a finished value too, and
+// pairs the same operations.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -94,10 +96,10 @@ __device__ __forceinline__ T semi_sq_line(const T* __restrict__ x, int64_t n, in
 }
 
 // The analytic form's sums of products, with their roundings spelled out: one fused multiply-add
-// per axis onto the finished sum of the axes before it, which is how hipcc contracts the forward's
-// loops over loaded coordinates.  A kernel that holds the coordinates in registers gets the
-// products hoisted, selected or paired another way if the pairing is left to the compiler, so
-// contraction is off here and the forward's pairing is written out.
+// per axis onto the finished sum of the axes before it.  That pairing is the definition: contraction
+// is off here and every fused multiply-add is written out, so the element does not depend on how
+// hipcc would pair the products of a kernel that holds the coordinates in registers (hoisted,
+// selected or fused another way from kernel to kernel).
 __device__ __forceinline__ float semi_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double semi_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 

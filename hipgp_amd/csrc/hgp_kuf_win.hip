@@ -13,8 +13,8 @@
 // the predicate's own comparisons find exactly the set the predicate describes (win_first).  The
 // matvec finds the ranges that way, the rmatvec applies the predicate pair by pair: one set, so
 // the two products are exact transposes.  The element value is formed in one way in both
-// (win_axis, win_outer, one fused multiply-add for the last axis, kern_eval), so it has the same
-// bits in both.
+// (kuf_axis, kuf_outer, one fused multiply-add for the last axis: hgp_kuf_eval.hpp), so it has the
+// same bits in both.
 //
 // k_kuf_win_mv: one wave per point, four points a block, no LDS and no barrier.  Lanes 0 .. 2d-1
 // run the 2d searches side by side and the wave reads their results.  The wave then walks the
@@ -23,9 +23,9 @@
 // dtype, the rows in fp64; the lanes are added by the fixed xor butterfly.  Weight rows in groups
 // of 8, 4 or 1 as the dense kernel.  No atomics.
 //
-// k_kuf_win_rmv: a gather.  A block of 256 threads owns a tile of mesh points (256 | 16 x 16 |
-// 4 x 8 x 8), one per thread.  The observations come sorted by BIN: per axis the cell of x is the
-// number of nodes <= x (0 .. m), its bin is cell / tile, bins are numbered in C order (kuf_win_bins).
+// k_kuf_win_rmv: a gather.  A block owns a tile of mesh points (KufTile, hgp_kuf_tile.hpp), one
+// per thread.  The observations come sorted by BIN: per axis the cell of x is the number of nodes
+// <= x (0 .. m), its bin is cell / tile, bins are numbered in C order (kuf_win_bins).
 // Only x in [g[first] - rho, g[last] + rho] can reach a tile on an axis; the block finds the cells of
 // those two ends (the interval widened by 1e-6 rho and 1e-15 |g|, far more than the predicate's
 // rounding, in fp64) and visits the bins between.  The bins of one last-axis row are neighbours in
@@ -41,21 +41,13 @@
 #include <limits>
 
 #include "hgp_kuf_eval.hpp"
+#include "hgp_kuf_launch.hpp"
+#include "hgp_kuf_tile.hpp"
 
 namespace hgp {
 
-constexpr int WIN_THREADS = 256;   // block of both kernels: 4 points (mv), one tile of mesh points (rmv)
+constexpr int WIN_THREADS = KUF_TILE_THREADS;   // block of both kernels: 4 points (mv), one tile of mesh points (rmv)
 constexpr int WIN_CHUNK = 256;     // observations staged at once (rmv); the longest run summed in dtype
-
-// mesh points of a tile along each axis; the bins are cells in groups of the same width
-__host__ __device__ inline int win_tile(int ndim, int a) {
-  if (ndim == 1) return a == 0 ? 256 : 1;
-  if (ndim == 2) return a < 2 ? 16 : 1;
-  return a == 0 ? 4 : 8;
-}
-
-__device__ __forceinline__ float win_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double win_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // the window's predicate on one axis
 template <typename T>
@@ -77,24 +69,6 @@ __device__ __forceinline__ int64_t win_first(const T* __restrict__ g, int64_t m,
       a = mid + 1;
   }
   return a;
-}
-
-// the scaled difference of one axis, as k_kuf_grid forms it
-template <typename T, int KIND>
-__device__ __forceinline__ T win_axis(T x, T u, T ell) {
-  T dv = x - u;
-  if (KIND == HGP_KERN_SQEXP) dv = dv / ell;
-  return dv;
-}
-
-// the outer axes' squared distance; the whole is win_fma(dl, dl, win_outer(...)) in both kernels
-// (d = 1: fma(dl, dl, 0) has the bits of dl * dl)
-template <typename T>
-__device__ __forceinline__ T win_outer(int d, T d0, T d1) {
-#pragma clang fp contract(off)
-  if (d == 1) return (T)0;
-  if (d == 2) return d0 * d0;
-  return win_fma(d0, d0, d1 * d1);
 }
 
 template <typename T, int KIND, int NW>
@@ -134,17 +108,17 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_mv(KufGrid g, const T* 
 #pragma unroll
   for (int s = 0; s < NW; ++s) acc[s] = 0;
   for (int64_t o0 = a0; o0 < b0; ++o0) {
-    const T d0 = d >= 2 ? win_axis<T, KIND>(x0, g0[o0], ell) : (T)0;
+    const T d0 = d >= 2 ? kuf_axis<T, KIND>(x0, g0[o0], ell) : (T)0;
     for (int64_t o1 = a1; o1 < b1; ++o1) {
-      const T d1 = d == 3 ? win_axis<T, KIND>(x1, g1[o1], ell) : (T)0;
-      const T so = win_outer<T>(d, d0, d1);
+      const T d1 = d == 3 ? kuf_axis<T, KIND>(x1, g1[o1], ell) : (T)0;
+      const T so = kuf_outer<T>(d, d0, d1);
       const int64_t base = (d == 3 ? o0 * m1 + o1 : (d == 2 ? o0 : 0)) * inner;
       T run[NW];
 #pragma unroll
       for (int s = 0; s < NW; ++s) run[s] = 0;
       for (int64_t i = loL + lane; i < hiL; i += 64) {
-        const T dv = win_axis<T, KIND>(xl, gl[i], ell);
-        const T kv = kern_eval<T>(KIND, win_fma(dv, dv, so), sig2, ell);
+        const T dv = kuf_axis<T, KIND>(xl, gl[i], ell);
+        const T kv = kern_eval<T>(KIND, kuf_fma(dv, dv, so), sig2, ell);
 #pragma unroll
         for (int s = 0; s < NW; ++s) run[s] += kv * wp[s][base + i];
       }
@@ -186,20 +160,15 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
   __shared__ T xs[D][WIN_CHUNK];
   __shared__ T cs[NC][WIN_CHUNK];
   __shared__ int64_t cell_s[2 * D];
-  constexpr int T0 = D == 1 ? 256 : (D == 2 ? 16 : 4);       // win_tile(D, .)
-  constexpr int T1 = D == 1 ? 1 : (D == 2 ? 16 : 8);
-  constexpr int T2 = D == 3 ? 8 : 1;
+  constexpr int T0 = KufTile<D>::T0, T1 = KufTile<D>::T1, T2 = KufTile<D>::T2;
   const int tid = threadIdx.x;
-  const int64_t m0 = g.m[0], m1 = D > 1 ? g.m[1] : 1, m2 = D > 2 ? g.m[2] : 1;
+  // the block's tile and the thread's mesh point in it
+  const KufTilePos tp = kuf_tile_pos<D>(g);
+  const int64_t m0 = tp.m0, m1 = tp.m1, m2 = tp.m2, i0 = tp.i0, i1 = tp.i1, i2 = tp.i2;
+  const bool live = tp.live;
   const T* g0 = reinterpret_cast<const T*>(g.g[0]);
   const T* g1 = reinterpret_cast<const T*>(g.g[D > 1 ? 1 : 0]);
   const T* g2 = reinterpret_cast<const T*>(g.g[D > 2 ? 2 : 0]);
-  // the block's tile (C order over the tiles of the axes) and the thread's mesh point in it
-  const int64_t nt1 = (m1 + T1 - 1) / T1, nt2 = (m2 + T2 - 1) / T2;
-  const int64_t bt = blockIdx.x;
-  const int64_t t0 = bt / (nt1 * nt2), t1 = (bt / nt2) % nt1, t2 = bt % nt2;
-  const int64_t i0 = t0 * T0 + tid / (T1 * T2), i1 = t1 * T1 + (tid / T2) % T1, i2 = t2 * T2 + tid % T2;
-  const bool live = i0 < m0 && i1 < m1 && i2 < m2;
   const T u0 = g0[i0 < m0 ? i0 : m0 - 1];
   const T u1 = D > 1 ? g1[i1 < m1 ? i1 : m1 - 1] : (T)0;
   const T u2 = D > 2 ? g2[i2 < m2 ? i2 : m2 - 1] : (T)0;
@@ -208,7 +177,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
     const int a = tid >> 1;
     const T* ga = a == 0 ? g0 : (a == 1 ? g1 : g2);
     const int64_t ma = a == 0 ? m0 : (a == 1 ? m1 : m2);
-    const int64_t first = a == 0 ? t0 * T0 : (a == 1 ? t1 * T1 : t2 * T2);
+    const int64_t first = a == 0 ? tp.t0 * T0 : (a == 1 ? tp.t1 * T1 : tp.t2 * T2);
     int64_t last = first + (a == 0 ? T0 : (a == 1 ? T1 : T2)) - 1;
     if (last > ma - 1) last = ma - 1;
     const double rw = (double)rho * (1.0 + 1e-6);
@@ -261,10 +230,10 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
             if (D > 1) in = in && win_in<T>(p1, u1, rho);
             if (D > 2) in = in && win_in<T>(p2, u2, rho);
             if (in) {
-              const T d0 = D >= 2 ? win_axis<T, KIND>(p0, u0, ell) : (T)0;
-              const T d1 = D == 3 ? win_axis<T, KIND>(p1, u1, ell) : (T)0;
-              const T dv = win_axis<T, KIND>(D == 1 ? p0 : (D == 2 ? p1 : p2), ul, ell);
-              const T kv = kern_eval<T>(KIND, win_fma(dv, dv, win_outer<T>(D, d0, d1)), sig2, ell);
+              const T d0 = D >= 2 ? kuf_axis<T, KIND>(p0, u0, ell) : (T)0;
+              const T d1 = D == 3 ? kuf_axis<T, KIND>(p1, u1, ell) : (T)0;
+              const T dv = kuf_axis<T, KIND>(D == 1 ? p0 : (D == 2 ? p1 : p2), ul, ell);
+              const T kv = kern_eval<T>(KIND, kuf_sqdist<T>(D, d0, d1, dv), sig2, ell);
 #pragma unroll
               for (int s = 0; s < NC; ++s) run[s] += kv * cs[s][k];
             }
@@ -276,65 +245,10 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
     }
   }
   if (!live) return;
-  const int64_t j = (D == 1 ? i0 : (D == 2 ? i0 * m1 + i1 : (i0 * m1 + i1) * m2 + i2));
+  const int64_t j = tp.flat<D>();
 #pragma unroll
   for (int s = 0; s < NC; ++s)
     if (s < ncv) out[(int64_t)s * M + j] = (T)acc[s];
-}
-
-// the width of the next group of weight / coefficient rows, as the dense products
-static inline int win_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
-
-template <typename T, int KIND>
-static void launch_win_mv(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2, T ell,
-                          T rho, const T* w, int nwv, int64_t M, T* out, int64_t ldo) {
-  if (NW == 8)
-    hipLaunchKernelGGL((k_kuf_win_mv<T, KIND, 8>), dim3(nb), dim3(WIN_THREADS), 0, s, g, x, B, sig2, ell, rho, w, nwv,
-                       M, out, ldo);
-  else if (NW == 4)
-    hipLaunchKernelGGL((k_kuf_win_mv<T, KIND, 4>), dim3(nb), dim3(WIN_THREADS), 0, s, g, x, B, sig2, ell, rho, w, nwv,
-                       M, out, ldo);
-  else
-    hipLaunchKernelGGL((k_kuf_win_mv<T, KIND, 1>), dim3(nb), dim3(WIN_THREADS), 0, s, g, x, B, sig2, ell, rho, w, nwv,
-                       M, out, ldo);
-}
-
-template <typename T, int KIND, int D>
-static void launch_win_rmv_d(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2,
-                             T ell, T rho, const T* c, int ncv, int64_t M, const int64_t* order,
-                             const int64_t* bin_start, T* out) {
-  if (NC == 8)
-    hipLaunchKernelGGL((k_kuf_win_rmv<T, KIND, 8, D>), dim3(nb), dim3(WIN_THREADS), 0, s, g, x, B, sig2, ell, rho, c,
-                       ncv, M, order, bin_start, out);
-  else if (NC == 4)
-    hipLaunchKernelGGL((k_kuf_win_rmv<T, KIND, 4, D>), dim3(nb), dim3(WIN_THREADS), 0, s, g, x, B, sig2, ell, rho, c,
-                       ncv, M, order, bin_start, out);
-  else
-    hipLaunchKernelGGL((k_kuf_win_rmv<T, KIND, 1, D>), dim3(nb), dim3(WIN_THREADS), 0, s, g, x, B, sig2, ell, rho, c,
-                       ncv, M, order, bin_start, out);
-}
-
-template <typename T, int KIND>
-static void launch_win_rmv(int NC, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, T sig2, T ell,
-                           T rho, const T* c, int ncv, int64_t M, const int64_t* order, const int64_t* bin_start,
-                           T* out) {
-  if (g.d == 1)
-    launch_win_rmv_d<T, KIND, 1>(NC, nb, s, g, x, B, sig2, ell, rho, c, ncv, M, order, bin_start, out);
-  else if (g.d == 2)
-    launch_win_rmv_d<T, KIND, 2>(NC, nb, s, g, x, B, sig2, ell, rho, c, ncv, M, order, bin_start, out);
-  else
-    launch_win_rmv_d<T, KIND, 3>(NC, nb, s, g, x, B, sig2, ell, rho, c, ncv, M, order, bin_start, out);
-}
-
-static int64_t win_grid(KufGrid& g, int ndim, const int64_t* m, const void* const* grids) {
-  g.d = ndim;
-  int64_t M = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    M *= m[a];
-  }
-  return M;
 }
 
 // nobs > 0, nw > 0
@@ -343,7 +257,8 @@ static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const v
                                    int64_t nobs, double sig2, double ell, double rho, const void* wv, int64_t nw,
                                    void* outv, hipStream_t s) {
   KufGrid g{};
-  const int64_t M = win_grid(g, ndim, m, grids);
+  int64_t M;
+  kuf_fill_grid(g, ndim, m, grids, &M);
   const T* x = reinterpret_cast<const T*>(xv);
   const T* w = reinterpret_cast<const T*>(wv);
   T* out = reinterpret_cast<T*>(outv);
@@ -351,27 +266,14 @@ static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const v
   const int64_t nblk = (nobs + per - 1) / per;
   if (nblk > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)nblk;
-  for (int64_t s0 = 0; s0 < nw;) {
-    const int NW = win_group(nw - s0);
-    const int nwv = (int)(nw - s0 < NW ? nw - s0 : NW);
-    const T* wg = w + s0 * M;
-    T* og = out + s0;
-    switch (kind) {
-      case HGP_KERN_SQEXP:
-        launch_win_mv<T, HGP_KERN_SQEXP>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, wg, nwv, M, og, nw);
-        break;
-      case HGP_KERN_MATERN12:
-        launch_win_mv<T, HGP_KERN_MATERN12>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, wg, nwv, M, og, nw);
-        break;
-      case HGP_KERN_MATERN32:
-        launch_win_mv<T, HGP_KERN_MATERN32>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, wg, nwv, M, og, nw);
-        break;
-      default:
-        launch_win_mv<T, HGP_KERN_MATERN52>(NW, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, wg, nwv, M, og, nw);
-    }
-    s0 += nwv;
-  }
-  return hipGetLastError();
+  return kuf_row_groups(nw, s, [&](int64_t s0, int NW, int nwv, double*) {
+    kuf_with_kind(kind, [&](auto K) {
+      kuf_with_width(NW, [&](auto W) {
+        hipLaunchKernelGGL((k_kuf_win_mv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(WIN_THREADS), 0,
+                           s, g, x, nobs, (T)sig2, (T)ell, (T)rho, w + s0 * M, nwv, M, out + s0, nw);
+      });
+    });
+  });
 }
 
 // nobs >= 0 (0: out zeroed), nc > 0
@@ -380,40 +282,26 @@ static hipError_t kuf_rmatvec_win_t(int kind, int ndim, const int64_t* m, const 
                                     int64_t nobs, double sig2, double ell, double rho, const void* cv, int64_t nc,
                                     const int64_t* order, const int64_t* bin_start, void* outv, hipStream_t s) {
   KufGrid g{};
-  const int64_t M = win_grid(g, ndim, m, grids);
+  int64_t M;
+  kuf_fill_grid(g, ndim, m, grids, &M);
   T* out = reinterpret_cast<T*>(outv);
   if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
   const T* x = reinterpret_cast<const T*>(xv);
   const T* c = reinterpret_cast<const T*>(cv);
-  int64_t ntile = 1;
-  for (int a = 0; a < ndim; ++a) ntile *= (m[a] + win_tile(ndim, a) - 1) / win_tile(ndim, a);
+  const int64_t ntile = kuf_tile_count(ndim, m);
   if (ntile > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)ntile;
-  for (int64_t s0 = 0; s0 < nc;) {
-    const int NC = win_group(nc - s0);
-    const int ncv = (int)(nc - s0 < NC ? nc - s0 : NC);
-    const T* cg = c + s0 * nobs;
-    T* og = out + s0 * M;
-    switch (kind) {
-      case HGP_KERN_SQEXP:
-        launch_win_rmv<T, HGP_KERN_SQEXP>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, cg, ncv, M, order,
-                                          bin_start, og);
-        break;
-      case HGP_KERN_MATERN12:
-        launch_win_rmv<T, HGP_KERN_MATERN12>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, cg, ncv, M, order,
-                                             bin_start, og);
-        break;
-      case HGP_KERN_MATERN32:
-        launch_win_rmv<T, HGP_KERN_MATERN32>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, cg, ncv, M, order,
-                                             bin_start, og);
-        break;
-      default:
-        launch_win_rmv<T, HGP_KERN_MATERN52>(NC, nb, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, cg, ncv, M, order,
-                                             bin_start, og);
-    }
-    s0 += ncv;
-  }
-  return hipGetLastError();
+  return kuf_row_groups(nc, s, [&](int64_t s0, int NC, int ncv, double*) {
+    kuf_with_kind(kind, [&](auto K) {
+      kuf_with_dim(ndim, [&](auto D) {
+        kuf_with_width(NC, [&](auto W) {
+          hipLaunchKernelGGL((k_kuf_win_rmv<T, decltype(K)::value, decltype(W)::value, decltype(D)::value>), dim3(nb),
+                             dim3(WIN_THREADS), 0, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, c + s0 * nobs, ncv, M,
+                             order, bin_start, out + s0 * M);
+        });
+      });
+    });
+  });
 }
 
 // launcher behind hgp_kuf_grid_matvec_win
@@ -438,7 +326,7 @@ hipError_t kuf_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, cons
 // m[a] / tile[a] + 1 bins of tile[a] cells (cells 0 .. m[a]); axes >= ndim: 1 and 1
 void kuf_win_geometry(int ndim, const int64_t* m, int64_t* tile, int64_t* nbins) {
   for (int a = 0; a < 3; ++a) {
-    tile[a] = a < ndim ? win_tile(ndim, a) : 1;
+    tile[a] = a < ndim ? kuf_tile(ndim, a) : 1;
     nbins[a] = a < ndim ? m[a] / tile[a] + 1 : 1;
   }
 }

@@ -12,7 +12,8 @@
 // indexed by the feature (omega, phase, the w values) is the same for all lanes, so those loads are
 // wave-uniform (scalar loads, no LDS).  One cosine feeds NW fused multiply-adds.  nw > 8 runs in
 // groups of weight rows (8, 4 or 1 wide; a group's unused slots repeat its last row and are not
-// written).
+// written).  The host scaffold (CU count, row groups, partials, the width ladder) is
+// hgp_kuf_launch.hpp's; what the two products here share beyond it is rff_products.
 //
 // The cosine: the argument is formed in revolutions, reduced to [0, 1) by its fractional part (one
 // instruction, exact) and handed to the hardware cosine, which takes revolutions.  At a length
@@ -39,6 +40,7 @@
 #include <stdint.h>
 
 #include "hgp_kuf_eval.hpp"
+#include "hgp_kuf_launch.hpp"
 
 namespace hgp {
 
@@ -159,63 +161,19 @@ __global__ __launch_bounds__(256) void k_rff_finish(const double* __restrict__ p
   rff_store<T>(out, o, n, s, a);
 }
 
-static int rff_cus(hipError_t* e) {
-  static int cus[64] = {0};
-  int dev = 0;
-  *e = hipGetDevice(&dev);
-  if (*e != hipSuccess) return 0;
-  if (dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int v = 0;
-    *e = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev);
-    if (*e != hipSuccess) return 0;
-    cus[dev] = v > 0 ? v : 256;
-  }
-  return cus[dev];
-}
-
-// the width of the next group of weight rows
-static inline int rff_group(int64_t rem) { return rem >= 5 ? 8 : (rem >= 2 ? 4 : 1); }
-
-template <typename T>
-static void launch_rff(int NW, unsigned nb, hipStream_t s, const KufGrid& g, const T* x, int64_t B, const T* omega,
-                       const T* phase, int64_t F, const T* w, int nwv, int nsplit, int64_t nunit, double* part,
-                       T* out, const RffOut& o) {
-  if (NW == 8)
-    hipLaunchKernelGGL((k_rff_mv<T, 8>), dim3(nb), dim3(RFF_TILE), 0, s, g, x, B, omega, phase, F, w, nwv, nsplit,
-                       nunit, part, out, o);
-  else if (NW == 4)
-    hipLaunchKernelGGL((k_rff_mv<T, 4>), dim3(nb), dim3(RFF_TILE), 0, s, g, x, B, omega, phase, F, w, nwv, nsplit,
-                       nunit, part, out, o);
-  else
-    hipLaunchKernelGGL((k_rff_mv<T, 1>), dim3(nb), dim3(RFF_TILE), 0, s, g, x, B, omega, phase, F, w, nwv, nsplit,
-                       nunit, part, out, o);
-}
-
-// B > 0 points, F > 0 features, nw > 0 rows, nsplit >= 0; x == nullptr: the mesh of (m, grids)
-template <typename T>
-static hipError_t rff_matvec_t(int ndim, const int64_t* m, const void* const* grids, const void* xv, int64_t B,
-                               const void* omv, const void* phv, int64_t F, const void* wv, int64_t nw, double scale,
-                               int transposed, double beta, int64_t nsplit_in, void* outv, hipStream_t s) {
-  KufGrid g{};
-  g.d = ndim;
-  if (xv == nullptr)
-    for (int a = 0; a < ndim; ++a) {
-      g.m[a] = m[a];
-      g.g[a] = grids[a];
-    }
-  const T* x = reinterpret_cast<const T*>(xv);
-  const T* omega = reinterpret_cast<const T*>(omv);
-  const T* phase = reinterpret_cast<const T*>(phv);
-  const T* w = reinterpret_cast<const T*>(wv);
-  T* out = reinterpret_cast<T*>(outv);
-  // the split: a pure function of (B, F) and the CU count unless the caller forces it
+// What the two products share on the host: the split (a pure function of (B, F) and the CU count
+// unless the caller forces it), the partials and the groups of weight rows.  launch(W, nb, s0, nwv,
+// nsplit, nunit, part, og, o) starts the product's kernel for the group of rows from s0 on, W the
+// group's width as a constant.  B > 0, F > 0, nw > 0, nsplit >= 0.
+template <typename T, typename L>
+static hipError_t rff_products(int64_t B, int64_t F, int64_t nw, double scale, int transposed, double beta,
+                               int64_t nsplit_in, T* out, hipStream_t s, L&& launch) {
   const int64_t nunit = (F + RFF_UNIT - 1) / RFF_UNIT;
   const int64_t nrow = (B + RFF_TILE - 1) / RFF_TILE;                          // blocks per slice
   int64_t nsplit = nsplit_in;
   if (nsplit == 0) {
     hipError_t e = hipSuccess;
-    const int64_t target = (int64_t)16 * rff_cus(&e);                          // blocks that fill the device
+    const int64_t target = (int64_t)16 * kuf_cus(&e);                          // blocks that fill the device
     if (e != hipSuccess) return e;
     nsplit = (target + nrow - 1) / nrow;
     if (nsplit > nunit / RFF_MIN_UNITS) nsplit = nunit / RFF_MIN_UNITS;
@@ -224,35 +182,41 @@ static hipError_t rff_matvec_t(int ndim, const int64_t* m, const void* const* gr
   if (nsplit > nunit) nsplit = nunit;
   if (nrow * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)(nrow * nsplit);
-  double* part = nullptr;
-  if (nsplit > 1) {
-    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part),
-                                  (size_t)nsplit * (size_t)B * (size_t)rff_group(nw) * sizeof(double), s);
-    if (e != hipSuccess) return e;
-  }
   RffOut o{};
   o.sn = transposed ? 1 : nw;
   o.ss = transposed ? B : 1;
   o.scale = scale;
   o.beta = beta;
-  for (int64_t s0 = 0; s0 < nw;) {
-    const int NW = rff_group(nw - s0);
-    const int nwv = (int)(nw - s0 < NW ? nw - s0 : NW);
-    T* og = out + s0 * o.ss;
-    launch_rff<T>(NW, nb, s, g, x, B, omega, phase, F, w + s0 * F, nwv, (int)nsplit, nunit, part, og, o);
-    if (part != nullptr) {
-      const int64_t tot = B * NW;
-      hipLaunchKernelGGL((k_rff_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part, (int)nsplit,
-                         B, NW, nwv, og, o);
-    }
-    s0 += nwv;
-  }
-  hipError_t e = hipGetLastError();
-  if (part != nullptr) {
-    const hipError_t f = hipFreeAsync(part, s);
-    if (e == hipSuccess) e = f;
-  }
-  return e;
+  return kuf_row_groups(
+      nw, nsplit > 1 ? (size_t)nsplit * (size_t)B : 0, s,
+      [&](int64_t s0, int NW, int nwv, double* part) {
+        kuf_with_width(NW, [&](auto W) { launch(W, nb, s0, nwv, (int)nsplit, nunit, part, out + s0 * o.ss, o); });
+      },
+      [&](int64_t s0, int NW, int nwv, double* part) {
+        const int64_t tot = B * NW;
+        hipLaunchKernelGGL((k_rff_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part, (int)nsplit,
+                           B, NW, nwv, out + s0 * o.ss, o);
+      });
+}
+
+// x == nullptr: the mesh of (m, grids)
+template <typename T>
+static hipError_t rff_matvec_t(int ndim, const int64_t* m, const void* const* grids, const void* xv, int64_t B,
+                               const void* omv, const void* phv, int64_t F, const void* wv, int64_t nw, double scale,
+                               int transposed, double beta, int64_t nsplit, void* outv, hipStream_t s) {
+  KufGrid g{};
+  g.d = ndim;
+  if (xv == nullptr) kuf_fill_grid(g, ndim, m, grids);
+  const T* x = reinterpret_cast<const T*>(xv);
+  const T* omega = reinterpret_cast<const T*>(omv);
+  const T* phase = reinterpret_cast<const T*>(phv);
+  const T* w = reinterpret_cast<const T*>(wv);
+  return rff_products<T>(B, F, nw, scale, transposed, beta, nsplit, reinterpret_cast<T*>(outv), s,
+                         [&](auto W, unsigned nb, int64_t s0, int nwv, int ns, int64_t nunit, double* part, T* og,
+                             const RffOut& o) {
+                           hipLaunchKernelGGL((k_rff_mv<T, decltype(W)::value>), dim3(nb), dim3(RFF_TILE), 0, s, g, x,
+                                              B, omega, phase, F, w + s0 * F, nwv, ns, nunit, part, og, o);
+                         });
 }
 
 // launcher behind hgp_rff_matvec
@@ -370,74 +334,21 @@ __global__ __launch_bounds__(RFF_TILE) void k_rff_line_mv(int d, const T* __rest
   }
 }
 
-template <typename T>
-static void launch_rff_line(int NW, unsigned nb, hipStream_t s, int d, const T* x, int64_t B, const T* omega,
-                            const T* phase, int64_t F, const T* w, int nwv, int nsplit, int64_t nunit, double* part,
-                            T* out, const RffOut& o) {
-  if (NW == 8)
-    hipLaunchKernelGGL((k_rff_line_mv<T, 8>), dim3(nb), dim3(RFF_TILE), 0, s, d, x, B, omega, phase, F, w, nwv, nsplit,
-                       nunit, part, out, o);
-  else if (NW == 4)
-    hipLaunchKernelGGL((k_rff_line_mv<T, 4>), dim3(nb), dim3(RFF_TILE), 0, s, d, x, B, omega, phase, F, w, nwv, nsplit,
-                       nunit, part, out, o);
-  else
-    hipLaunchKernelGGL((k_rff_line_mv<T, 1>), dim3(nb), dim3(RFF_TILE), 0, s, d, x, B, omega, phase, F, w, nwv, nsplit,
-                       nunit, part, out, o);
-}
-
-// B > 0 rows of x, F > 0 features, nw > 0 rows, nsplit >= 0: the split, the scratch and the groups of rff_matvec_t
+// B > 0 rows of x; the rest as rff_matvec_t
 template <typename T>
 static hipError_t rff_line_matvec_t(int ndim, const void* xv, int64_t B, const void* omv, const void* phv, int64_t F,
                                     const void* wv, int64_t nw, double scale, int transposed, double beta,
-                                    int64_t nsplit_in, void* outv, hipStream_t s) {
+                                    int64_t nsplit, void* outv, hipStream_t s) {
   const T* x = reinterpret_cast<const T*>(xv);
   const T* omega = reinterpret_cast<const T*>(omv);
   const T* phase = reinterpret_cast<const T*>(phv);
   const T* w = reinterpret_cast<const T*>(wv);
-  T* out = reinterpret_cast<T*>(outv);
-  const int64_t nunit = (F + RFF_UNIT - 1) / RFF_UNIT;
-  const int64_t nrow = (B + RFF_TILE - 1) / RFF_TILE;                          // blocks per slice
-  int64_t nsplit = nsplit_in;
-  if (nsplit == 0) {
-    hipError_t e = hipSuccess;
-    const int64_t target = (int64_t)16 * rff_cus(&e);                          // blocks that fill the device
-    if (e != hipSuccess) return e;
-    nsplit = (target + nrow - 1) / nrow;
-    if (nsplit > nunit / RFF_MIN_UNITS) nsplit = nunit / RFF_MIN_UNITS;
-    if (nsplit < 1) nsplit = 1;
-  }
-  if (nsplit > nunit) nsplit = nunit;
-  if (nrow * nsplit > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  const unsigned nb = (unsigned)(nrow * nsplit);
-  double* part = nullptr;
-  if (nsplit > 1) {
-    hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part),
-                                  (size_t)nsplit * (size_t)B * (size_t)rff_group(nw) * sizeof(double), s);
-    if (e != hipSuccess) return e;
-  }
-  RffOut o{};
-  o.sn = transposed ? 1 : nw;
-  o.ss = transposed ? B : 1;
-  o.scale = scale;
-  o.beta = beta;
-  for (int64_t s0 = 0; s0 < nw;) {
-    const int NW = rff_group(nw - s0);
-    const int nwv = (int)(nw - s0 < NW ? nw - s0 : NW);
-    T* og = out + s0 * o.ss;
-    launch_rff_line<T>(NW, nb, s, ndim, x, B, omega, phase, F, w + s0 * F, nwv, (int)nsplit, nunit, part, og, o);
-    if (part != nullptr) {
-      const int64_t tot = B * NW;
-      hipLaunchKernelGGL((k_rff_finish<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, part, (int)nsplit,
-                         B, NW, nwv, og, o);
-    }
-    s0 += nwv;
-  }
-  hipError_t e = hipGetLastError();
-  if (part != nullptr) {
-    const hipError_t f = hipFreeAsync(part, s);
-    if (e == hipSuccess) e = f;
-  }
-  return e;
+  return rff_products<T>(B, F, nw, scale, transposed, beta, nsplit, reinterpret_cast<T*>(outv), s,
+                         [&](auto W, unsigned nb, int64_t s0, int nwv, int ns, int64_t nunit, double* part, T* og,
+                             const RffOut& o) {
+                           hipLaunchKernelGGL((k_rff_line_mv<T, decltype(W)::value>), dim3(nb), dim3(RFF_TILE), 0, s,
+                                              ndim, x, B, omega, phase, F, w + s0 * F, nwv, ns, nunit, part, og, o);
+                         });
 }
 
 // launcher behind hgp_rff_line_matvec
