@@ -41,6 +41,8 @@ EXPORTS = (
     "hgp_kuf_grid_matvec_win", "hgp_kuf_grid_rmatvec_win", "hgp_kuf_win_bins",
     "hgp_kuf_semi_mc_matvec_win", "hgp_kuf_semi_sqexp_matvec_win",
     "hgp_kuf_semi_mc_rmatvec_win", "hgp_kuf_semi_sqexp_rmatvec_win",
+    "hgp_kuf_grid_ard", "hgp_kuf_grid_matvec_ard", "hgp_kuf_grid_rmatvec_ard",
+    "hgp_kuf_grid_matvec_win_ard", "hgp_kuf_grid_rmatvec_win_ard", "hgp_kuf_grid_grad_ard",
 )
 KERN_SQEXP, KERN_MATERN12, KERN_MATERN32, KERN_MATERN52, KERN_GNEITING = 0, 1, 2, 3, 4
 
@@ -62,6 +64,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     vp, i64, i32, dbl = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double
     pi64, pi32 = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)
+    pdbl = ctypes.POINTER(dbl)
     sig = {
         "hgp_plan_create": (i32, [i32, i32, pi64, i32, i64, vp, ctypes.POINTER(vp)]),
         "hgp_plan_set_stream": (i32, [vp, vp]),
@@ -110,6 +113,17 @@ def lib():
         "hgp_kuf_grid_rmatvec_win": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, vp, i64, vp,
                                            vp, vp, vp]),
         "hgp_kuf_win_bins": (i32, [i32, pi64, pi64, pi64]),
+        # one ell (and rho) per axis: the scalar entries' signatures with host double arrays in their place
+        "hgp_kuf_grid_ard": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, pdbl, vp, vp]),
+        "hgp_kuf_grid_grad_ard": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, pdbl, vp, vp, vp]),
+        "hgp_kuf_grid_matvec_ard": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, pdbl, vp, i64, i64, vp,
+                                          vp]),
+        "hgp_kuf_grid_rmatvec_ard": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, pdbl, vp, i64, i64, vp,
+                                           vp]),
+        "hgp_kuf_grid_matvec_win_ard": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, pdbl, pdbl, vp, i64,
+                                              vp, vp]),
+        "hgp_kuf_grid_rmatvec_win_ard": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, pdbl, pdbl, vp,
+                                               i64, vp, vp, vp, vp]),
         "hgp_kuf_semi_mc_matvec_win": (i32, [i32, i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, i32, vp,
                                              vp, i64, vp, i64, vp, vp]),
         "hgp_kuf_semi_sqexp_matvec_win": (i32, [i32, i32, pi64, ctypes.POINTER(vp), vp, i64, dbl, dbl, dbl, vp, i64,

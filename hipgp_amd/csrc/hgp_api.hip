@@ -2497,8 +2497,36 @@ int hgp_rowdot(int dtype, const void* a, const void* c, void* out, int64_t nrhs,
   return 0;
 }
 
-int hgp_kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                 int64_t nobs, double sig2, double ell, void* out, void* hip_stream) {
+// ---- one length scale (and one window radius) per axis: the point-observation launchers take three values ----
+// a scalar entry's ell or rho on every axis
+struct KufRep3 {
+  double v[3];
+  explicit KufRep3(double a) : v{a, a, a} {}
+};
+
+// What the _ard entries check ahead of the scalar entries' own checks, all before any HIP call: the kernel,
+// ndim (ell and rho hold ndim values), every ell[a] finite and > 0, every rho[a] finite and >= 0 (rho == nullptr
+// with want_rho == false: the entry has none).  e3 / r3: the values, the last one repeated on the absent axes.
+static int check_ard_args(int kind, int ndim, const double* ell, const double* rho, bool want_rho, double* e3,
+                          double* r3) {
+  if (kind != HGP_KERN_SQEXP) return fail(HGP_E_ARG, "a length scale per axis is defined for HGP_KERN_SQEXP only");
+  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
+  if (ell == nullptr || (want_rho && rho == nullptr)) return fail(HGP_E_ARG, "null ell / rho");
+  for (int a = 0; a < ndim; ++a) {
+    if (!(ell[a] > 0) || !std::isfinite(ell[a])) return fail(HGP_E_ARG, "every ell[a] must be finite and > 0");
+    if (want_rho && (!(rho[a] >= 0) || !std::isfinite(rho[a])))
+      return fail(HGP_E_ARG, "every rho[a] must be finite and >= 0");
+  }
+  for (int a = 0; a < 3; ++a) {
+    e3[a] = ell[a < ndim ? a : ndim - 1];
+    if (want_rho) r3[a] = rho[a < ndim ? a : ndim - 1];
+  }
+  return 0;
+}
+
+static int kuf_grid_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                          const void* x, int64_t nobs, double sig2, const double* ell3, void* out,
+                          void* hip_stream) {
   if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
   if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");
   if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
@@ -2506,9 +2534,21 @@ int hgp_kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* co
   if (nobs < 0 || x == nullptr || out == nullptr) return fail(HGP_E_ARG, "bad x/out/nobs");
   for (int a = 0; a < ndim; ++a)
     if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-  hipError_t e = kuf_grid(dtype, kind, ndim, m, grids, x, nobs, sig2, ell, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid: ") + hipGetErrorString(e));
+  hipError_t e = kuf_grid(dtype, kind, ndim, m, grids, x, nobs, sig2, ell3, out, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
   return 0;
+}
+
+int hgp_kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                 int64_t nobs, double sig2, double ell, void* out, void* hip_stream) {
+  return kuf_grid_entry("hgp_kuf_grid", dtype, kind, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, out, hip_stream);
+}
+
+int hgp_kuf_grid_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                     int64_t nobs, double sig2, const double* ell, void* out, void* hip_stream) {
+  double e3[3];
+  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
+  return kuf_grid_entry("hgp_kuf_grid_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, out, hip_stream);
 }
 
 static int check_grid_args(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
@@ -2569,6 +2609,16 @@ int hgp_kuf_grid_grad(int dtype, int kind, int ndim, const int64_t* m, const voi
   return 0;
 }
 
+int hgp_kuf_grid_grad_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                          int64_t nobs, double sig2, const double* ell, const void* g, void* grad, void* hip_stream) {
+  double e3[3];
+  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
+  HGP_TRY(check_grad_args(dtype, kind, ndim, m, grids, x, nobs, g, grad));
+  hipError_t e = kuf_grad_ard(dtype, ndim, m, grids, x, nobs, sig2, e3, g, grad, reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_grad_ard: ") + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_kuf_semi_mc_grad(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
                          const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u,
                          const void* g, void* grad2, void* hip_stream) {
@@ -2605,16 +2655,33 @@ static int check_matvec_args(int dtype, int ndim, const int64_t* m, const void* 
   return 0;
 }
 
-int hgp_kuf_grid_matvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                        int64_t nobs, double sig2, double ell, const void* w, int64_t nw, int64_t nsplit, void* out,
-                        void* hip_stream) {
+static int kuf_grid_matvec_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
+                                 const void* const* grids, const void* x, int64_t nobs, double sig2,
+                                 const double* ell3, const void* w, int64_t nw, int64_t nsplit, void* out,
+                                 void* hip_stream) {
   if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
   const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, nsplit, out);
   if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, w, nw, nsplit, out,
+  hipError_t e = kuf_matvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell3, 0, nullptr, w, nw, nsplit, out,
                             reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_matvec: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
   return 0;
+}
+
+int hgp_kuf_grid_matvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                        int64_t nobs, double sig2, double ell, const void* w, int64_t nw, int64_t nsplit, void* out,
+                        void* hip_stream) {
+  return kuf_grid_matvec_entry("hgp_kuf_grid_matvec", dtype, kind, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, w, nw,
+                               nsplit, out, hip_stream);
+}
+
+int hgp_kuf_grid_matvec_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                            int64_t nobs, double sig2, const double* ell, const void* w, int64_t nw, int64_t nsplit,
+                            void* out, void* hip_stream) {
+  double e3[3];
+  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
+  return kuf_grid_matvec_entry("hgp_kuf_grid_matvec_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, w, nw, nsplit,
+                               out, hip_stream);
 }
 
 int hgp_kuf_semi_mc_matvec(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
@@ -2625,7 +2692,7 @@ int hgp_kuf_semi_mc_matvec(int dtype, int kind, double kparam, int ndim, const i
   if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
   const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, nsplit, out);
   if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out,
+  hipError_t e = kuf_matvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, npts, u, w, nw, nsplit, out,
                             reinterpret_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_matvec: ") + hipGetErrorString(e));
   return 0;
@@ -2636,7 +2703,7 @@ int hgp_kuf_semi_sqexp_matvec(int dtype, int ndim, const int64_t* m, const void*
                               void* out, void* hip_stream) {
   const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, nsplit, out);
   if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, w, nw,
+  hipError_t e = kuf_matvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, 0, nullptr, w, nw,
                             nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_matvec: ") + hipGetErrorString(e));
   return 0;
@@ -2656,16 +2723,33 @@ static int check_rmatvec_args(int dtype, int ndim, const int64_t* m, const void*
   return 0;
 }
 
-int hgp_kuf_grid_rmatvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                         int64_t nobs, double sig2, double ell, const void* c, int64_t nc, int64_t nsplit, void* out,
-                         void* hip_stream) {
+static int kuf_grid_rmatvec_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
+                                  const void* const* grids, const void* x, int64_t nobs, double sig2,
+                                  const double* ell3, const void* c, int64_t nc, int64_t nsplit, void* out,
+                                  void* hip_stream) {
   if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
   const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
   if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_rmatvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, c, nc, nsplit, out,
+  hipError_t e = kuf_rmatvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell3, 0, nullptr, c, nc, nsplit, out,
                              reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_rmatvec: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
   return 0;
+}
+
+int hgp_kuf_grid_rmatvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                         int64_t nobs, double sig2, double ell, const void* c, int64_t nc, int64_t nsplit, void* out,
+                         void* hip_stream) {
+  return kuf_grid_rmatvec_entry("hgp_kuf_grid_rmatvec", dtype, kind, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, c,
+                                nc, nsplit, out, hip_stream);
+}
+
+int hgp_kuf_grid_rmatvec_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
+                             int64_t nobs, double sig2, const double* ell, const void* c, int64_t nc, int64_t nsplit,
+                             void* out, void* hip_stream) {
+  double e3[3];
+  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
+  return kuf_grid_rmatvec_entry("hgp_kuf_grid_rmatvec_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, c, nc,
+                                nsplit, out, hip_stream);
 }
 
 int hgp_kuf_semi_mc_rmatvec(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
@@ -2676,7 +2760,7 @@ int hgp_kuf_semi_mc_rmatvec(int dtype, int kind, double kparam, int ndim, const 
   if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
   const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
   if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_rmatvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out,
+  hipError_t e = kuf_rmatvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, npts, u, c, nc, nsplit, out,
                              reinterpret_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_rmatvec: ") + hipGetErrorString(e));
   return 0;
@@ -2687,7 +2771,7 @@ int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void
                                void* out, void* hip_stream) {
   const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
   if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_rmatvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, c, nc,
+  hipError_t e = kuf_rmatvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, 0, nullptr, c, nc,
                              nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_rmatvec: ") + hipGetErrorString(e));
   return 0;
@@ -2699,17 +2783,59 @@ static int check_win_rho(double rho) {
   return 0;
 }
 
+// the two windowed point products after the checks of the kernel and of rho, which differ between the scalar and the
+// _ard entries
+static int kuf_grid_matvec_win_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
+                                     const void* const* grids, const void* x, int64_t nobs, double sig2,
+                                     const double* ell3, const double* rho3, const void* w, int64_t nw, void* out,
+                                     void* hip_stream) {
+  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
+  if (c != 0) return c > 0 ? 0 : c;
+  hipError_t e = kuf_matvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell3, rho3, w, nw, out,
+                                reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
+  return 0;
+}
+
+static int kuf_grid_rmatvec_win_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
+                                      const void* const* grids, const void* x, int64_t nobs, double sig2,
+                                      const double* ell3, const double* rho3, const void* c, int64_t nc,
+                                      const int64_t* order, const int64_t* bin_start, void* out, void* hip_stream) {
+  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
+  if (r != 0) return r > 0 ? 0 : r;
+  if (nobs > 0 && (order == nullptr || bin_start == nullptr)) return fail(HGP_E_ARG, "null order / bin_start");
+  hipError_t e = kuf_rmatvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell3, rho3, c, nc, order, bin_start, out,
+                                 reinterpret_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
+  return 0;
+}
+
 int hgp_kuf_grid_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
                             int64_t nobs, double sig2, double ell, double rho, const void* w, int64_t nw, void* out,
                             void* hip_stream) {
   if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
   HGP_TRY(check_win_rho(rho));
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell, rho, w, nw, out,
-                                reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_matvec_win: ") + hipGetErrorString(e));
-  return 0;
+  return kuf_grid_matvec_win_entry("hgp_kuf_grid_matvec_win", dtype, kind, ndim, m, grids, x, nobs, sig2,
+                                   KufRep3(ell).v, KufRep3(rho).v, w, nw, out, hip_stream);
+}
+
+int hgp_kuf_grid_matvec_win_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                                const void* x, int64_t nobs, double sig2, const double* ell, const double* rho,
+                                const void* w, int64_t nw, void* out, void* hip_stream) {
+  double e3[3], r3[3];
+  HGP_TRY(check_ard_args(kind, ndim, ell, rho, true, e3, r3));
+  return kuf_grid_matvec_win_entry("hgp_kuf_grid_matvec_win_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, r3, w,
+                                   nw, out, hip_stream);
+}
+
+int hgp_kuf_grid_rmatvec_win_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                                 const void* x, int64_t nobs, double sig2, const double* ell, const double* rho,
+                                 const void* c, int64_t nc, const int64_t* order, const int64_t* bin_start, void* out,
+                                 void* hip_stream) {
+  double e3[3], r3[3];
+  HGP_TRY(check_ard_args(kind, ndim, ell, rho, true, e3, r3));
+  return kuf_grid_rmatvec_win_entry("hgp_kuf_grid_rmatvec_win_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, r3,
+                                    c, nc, order, bin_start, out, hip_stream);
 }
 
 int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
@@ -2717,13 +2843,8 @@ int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, co
                              const int64_t* order, const int64_t* bin_start, void* out, void* hip_stream) {
   if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
   HGP_TRY(check_win_rho(rho));
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  if (nobs > 0 && (order == nullptr || bin_start == nullptr)) return fail(HGP_E_ARG, "null order / bin_start");
-  hipError_t e = kuf_rmatvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell, rho, c, nc, order, bin_start, out,
-                                 reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_rmatvec_win: ") + hipGetErrorString(e));
-  return 0;
+  return kuf_grid_rmatvec_win_entry("hgp_kuf_grid_rmatvec_win", dtype, kind, ndim, m, grids, x, nobs, sig2,
+                                    KufRep3(ell).v, KufRep3(rho).v, c, nc, order, bin_start, out, hip_stream);
 }
 
 // the windowed line-integral products: the dense entries' checks, rho, the kernel and the piece counts

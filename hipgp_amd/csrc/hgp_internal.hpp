@@ -88,8 +88,10 @@ template <typename T> void extract_cplx(const double2* F, void* o, int64_t n, in
 template <typename T> void expand_spec(const double* src, void* out, const GridDims& g, hipStream_t s);
 
 // dense grid cross covariance (hgp_kuf.hip)
+// ell of the point-observation launchers (kuf_grid, kuf_matvec, kuf_rmatvec, the _win pair): three host values,
+// one per axis; SqExp divides axis a by ell[a], Matern and the line integrals read ell[0].  rho likewise.
 hipError_t kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                    int64_t nobs, double sig2, double ell, void* out, hipStream_t s);
+                    int64_t nobs, double sig2, const double* ell, void* out, hipStream_t s);
 hipError_t kuf_semi(int dtype, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
                     const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, void* out,
                     hipStream_t s);
@@ -99,22 +101,25 @@ hipError_t doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double 
 hipError_t kuf_grad(int dtype, int mode, int kind, int ndim, const int64_t* m, const void* const* grids,
                     const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* gup,
                     void* grad2, hipStream_t s);
+// SqExp point observations with one ell per axis: grad = (sum g dK/dsig2, sum g dK/dell_a for a < ndim)
+hipError_t kuf_grad_ard(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
+                        double sig2, const double* ell, const void* gup, void* grad, hipStream_t s);
 // out = Kuf w^T without Kuf (hgp_kuf_mv.hip); mode as kuf_grad; nobs > 0, nw > 0, nsplit >= 0 (0: chosen here)
 hipError_t kuf_matvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                      const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* w,
-                      int64_t nw, int64_t nsplit, void* out, hipStream_t s);
+                      const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
+                      const void* w, int64_t nw, int64_t nsplit, void* out, hipStream_t s);
 // out = c Kuf, the transposed product, without Kuf (hgp_kuf_rmv.hip); mode as kuf_grad; nobs >= 0 (0: out zeroed),
 // nc > 0, nsplit >= 0 (0: chosen here)
 hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                       const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* c,
-                       int64_t nc, int64_t nsplit, void* out, hipStream_t s);
-// the two point-observation products over the window |x - u| <= rho per axis (hgp_kuf_win.hip); matvec: nobs > 0,
+                       const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
+                       const void* c, int64_t nc, int64_t nsplit, void* out, hipStream_t s);
+// the two point-observation products over the window |x_a - u_a| <= rho[a] per axis (hgp_kuf_win.hip); matvec: nobs > 0,
 // nw > 0; rmatvec: nobs >= 0 (0: out zeroed), nc > 0, order / bin_start as kuf_win_geometry lays the bins out
 hipError_t kuf_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                          int64_t nobs, double sig2, double ell, double rho, const void* w, int64_t nw, void* out,
-                          hipStream_t s);
+                          int64_t nobs, double sig2, const double* ell, const double* rho, const void* w, int64_t nw,
+                          void* out, hipStream_t s);
 hipError_t kuf_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                           int64_t nobs, double sig2, double ell, double rho, const void* c, int64_t nc,
+                           int64_t nobs, double sig2, const double* ell, const double* rho, const void* c, int64_t nc,
                            const int64_t* order, const int64_t* bin_start, void* out, hipStream_t s);
 void kuf_win_geometry(int ndim, const int64_t* m, int64_t* tile, int64_t* nbins);
 // the two line-integral products over the window of a line: the nodes within rho of a piece of its segment

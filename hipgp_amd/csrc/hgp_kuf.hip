@@ -22,7 +22,7 @@ constexpr int KUF_CHUNK = KUF_THREADS * KUF_PER_THREAD;
 
 template <typename T>
 __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid(KufGrid g, const T* __restrict__ x, int64_t B, int kind,
-                                                         T sig2, T ell, T* __restrict__ out) {
+                                                         T sig2, KufVec<T> ell, T* __restrict__ out) {
   const int d = g.d;
   const int64_t inner = g.m[d - 1];
   const int64_t nchunk = (inner + KUF_CHUNK - 1) / KUF_CHUNK;
@@ -36,15 +36,16 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid(KufGrid g, const T* __
   if (n >= B) return;
   const bool sq = scaled_dist(kind);
   // outer axes: one scalar per block, summed in axis order (as the reference's sum over D)
-  auto sqd = [&](int a, int64_t ia) -> T {
+  auto sqd = [&](int a, int64_t ia, T el) -> T {
     T dv = x[n * d + a] - reinterpret_cast<const T*>(g.g[a])[ia];
-    if (sq) dv = dv / ell;
+    if (sq) dv = dv / el;
     return dv * dv;
   };
   T so = 0;
-  if (d == 2) so = sqd(0, o);
-  if (d == 3) so = sqd(0, o / g.m[1]) + sqd(1, o % g.m[1]);
+  if (d == 2) so = sqd(0, o, ell.v[0]);
+  if (d == 3) so = sqd(0, o / g.m[1], ell.v[0]) + sqd(1, o % g.m[1], ell.v[1]);
   const T xl = x[n * d + d - 1];
+  const T ell_l = kuf_last(ell, d);
   const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
   T* orow = out + (n * outer + o) * inner;
 #pragma unroll
@@ -52,9 +53,9 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid(KufGrid g, const T* __
     const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
     if (i < inner) {
       T dv = xl - gl[i];
-      if (sq) dv = dv / ell;
+      if (sq) dv = dv / ell_l;
       const T s = (d == 1) ? dv * dv : so + dv * dv;
-      orow[i] = kern_eval<T>(kind, s, sig2, ell);
+      orow[i] = kern_eval<T>(kind, s, sig2, ell.v[0]);
     }
   }
 }
@@ -223,9 +224,10 @@ hipError_t doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double 
   return hipGetLastError();
 }
 
-// launcher behind hgp_kuf_grid (argument checks in hgp_api.hip)
+// launcher behind hgp_kuf_grid / hgp_kuf_grid_ard (argument checks in hgp_api.hip); ell: one value per
+// axis, three in all (the scalar entry's value in each)
 hipError_t kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                    int64_t nobs, double sig2, double ell, void* out, hipStream_t s) {
+                    int64_t nobs, double sig2, const double* ell, void* out, hipStream_t s) {
   KufGrid g{};
   g.d = ndim;
   int64_t outer = 1;
@@ -239,11 +241,12 @@ hipError_t kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void*
   if (nb > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   if (dtype == HGP_F32)
     hipLaunchKernelGGL((k_kuf_grid<float>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g,
-                       reinterpret_cast<const float*>(x), nobs, kind, (float)sig2, (float)ell,
+                       reinterpret_cast<const float*>(x), nobs, kind, (float)sig2, kuf_vec<float>(ell),
                        reinterpret_cast<float*>(out));
   else
     hipLaunchKernelGGL((k_kuf_grid<double>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g,
-                       reinterpret_cast<const double*>(x), nobs, kind, sig2, ell, reinterpret_cast<double*>(out));
+                       reinterpret_cast<const double*>(x), nobs, kind, sig2, kuf_vec<double>(ell),
+                       reinterpret_cast<double*>(out));
   return hipGetLastError();
 }
 
@@ -361,6 +364,144 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid_grad(KufGrid g, const 
     }
   }
   kuf_block_sum2(a0, a1, part + 2 * (int64_t)blockIdx.x);
+}
+
+// ---- the same backward for SqExp with one length scale per axis (`kernels.py:73-79`) ------------
+// K = sig2 k0, k0 = e^{-s/2}, s = sum_a q_a, q_a = ((x_a - u_a) / ell_a)^2 formed as the forward
+// forms it.  dq_a/dell_a = -2 q_a / ell_a, so dK/dell_a = sig2 k0 q_a / ell_a: 1 + d sums
+//   part[0] = sum G k0,   part[1 + a] = sum G (k0 q_a / ell_a)
+// with the tiles, the block map and the fixed-order fp64 reduction of k_kuf_grid_grad.  k0 and the
+// first sum have that kernel's bits; with equal ell_a the per-axis sums add up to its dK/dell sum
+// to rounding (k0 s / ell there, the axes added here).
+constexpr int KUF_ARD_SUMS = 4;   // 1 + the most axes; a grid of fewer leaves the rest zero
+
+// wave (xor butterfly) then block (wave order) sum of KUF_ARD_SUMS values, as kuf_block_sum2
+__device__ __forceinline__ void kuf_block_sum4(double (&a)[KUF_ARD_SUMS], double* __restrict__ quad) {
+  __shared__ double red[KUF_ARD_SUMS][KUF_THREADS / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+    for (int q = 0; q < KUF_ARD_SUMS; ++q) a[q] += __shfl_xor(a[q], off, 64);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < KUF_ARD_SUMS; ++q) red[q][w] = a[q];
+  }
+  __syncthreads();
+  if (threadIdx.x < KUF_ARD_SUMS) {
+    double s = 0;
+    for (int k = 0; k < KUF_THREADS / 64; ++k) s += red[threadIdx.x][k];
+    quad[threadIdx.x] = s;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(KUF_THREADS) void k_kuf_grid_grad_ard(KufGrid g, const T* __restrict__ x, KufVec<T> ell,
+                                                                  const T* __restrict__ gup, int64_t ntile,
+                                                                  double* __restrict__ part) {
+  const int d = g.d;
+  const int64_t inner = g.m[d - 1];
+  const int64_t nchunk = (inner + KUF_CHUNK - 1) / KUF_CHUNK;
+  int64_t outer = 1;
+  for (int a = 0; a < d - 1; ++a) outer *= g.m[a];
+  const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
+  const T ell_l = kuf_last(ell, d);
+  double acc[KUF_ARD_SUMS] = {0, 0, 0, 0};
+  for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+    const int64_t chunk = t % nchunk;
+    const int64_t rest = t / nchunk;
+    const int64_t o = rest % outer;
+    const int64_t n = rest / outer;                         // < nobs: t < ntile = nobs * outer * nchunk
+    auto sqd = [&](int a, int64_t ia, T el) -> T {
+      const T dv = (x[n * d + a] - reinterpret_cast<const T*>(g.g[a])[ia]) / el;
+      return dv * dv;
+    };
+    T q0 = 0, q1 = 0, so = 0;
+    if (d == 2) {
+      q0 = sqd(0, o, ell.v[0]);
+      so = q0;
+    }
+    if (d == 3) {
+      q0 = sqd(0, o / g.m[1], ell.v[0]);
+      q1 = sqd(1, o % g.m[1], ell.v[1]);
+      so = q0 + q1;
+    }
+    const T xl = x[n * d + d - 1];
+    const T* grow = gup + (n * outer + o) * inner;
+#pragma unroll
+    for (int k = 0; k < KUF_PER_THREAD; ++k) {
+      const int64_t i = chunk * KUF_CHUNK + k * KUF_THREADS + threadIdx.x;
+      if (i < inner) {
+        const T dv = (xl - gl[i]) / ell_l;
+        const T ql = dv * dv;
+        const T s = (d == 1) ? ql : so + ql;
+        const T k0 = exp(-s / (T)2);
+        const T gv = grow[i];
+        acc[0] += (double)(gv * k0);
+        if (d >= 2) acc[1] += (double)(gv * (k0 * q0 / ell.v[0]));
+        if (d == 3) acc[2] += (double)(gv * (k0 * q1 / ell.v[1]));
+        const double tl = (double)(gv * (k0 * ql / ell_l));   // the last axis: slot d
+        if (d == 1)
+          acc[1] += tl;
+        else if (d == 2)
+          acc[2] += tl;
+        else
+          acc[3] += tl;
+      }
+    }
+  }
+  kuf_block_sum4(acc, part + KUF_ARD_SUMS * (int64_t)blockIdx.x);
+}
+
+// the sums of all blocks in a fixed order (fp64), times sig2 for the d/dell_a, in the tensor dtype
+template <typename T>
+__global__ __launch_bounds__(KUF_THREADS) void k_kuf_grad_finish_ard(const double* __restrict__ part, int np, int d,
+                                                                    double sig2, T* __restrict__ grad) {
+  __shared__ double tot[KUF_ARD_SUMS];
+  double acc[KUF_ARD_SUMS] = {0, 0, 0, 0};
+  for (int p = threadIdx.x; p < np; p += KUF_THREADS) {
+#pragma unroll
+    for (int q = 0; q < KUF_ARD_SUMS; ++q) acc[q] += part[KUF_ARD_SUMS * p + q];
+  }
+  kuf_block_sum4(acc, tot);
+  __syncthreads();
+  if (threadIdx.x == 0) grad[0] = (T)tot[0];
+  if (threadIdx.x >= 1 && (int)threadIdx.x <= d) grad[threadIdx.x] = (T)(sig2 * tot[threadIdx.x]);
+}
+
+template <typename T>
+static hipError_t kuf_grad_ard_t(int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
+                                 double sig2, const double* ell, const void* gup, void* grad, hipStream_t s) {
+  if (nobs == 0) return hipMemsetAsync(grad, 0, (size_t)(1 + ndim) * sizeof(T), s);
+  KufGrid g{};
+  g.d = ndim;
+  int64_t outer = 1;
+  for (int a = 0; a < ndim; ++a) {
+    g.m[a] = m[a];
+    g.g[a] = grids[a];
+    if (a < ndim - 1) outer *= m[a];
+  }
+  const int64_t nchunk = (m[ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK;
+  const int64_t ntile = nobs * outer * nchunk;
+  const int nblk = (int)(ntile < KUF_GRAD_BLOCKS ? ntile : KUF_GRAD_BLOCKS);
+  double* part = nullptr;
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)nblk * KUF_ARD_SUMS * sizeof(double), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_kuf_grid_grad_ard<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g,
+                     reinterpret_cast<const T*>(x), kuf_vec<T>(ell), reinterpret_cast<const T*>(gup), ntile, part);
+  hipLaunchKernelGGL((k_kuf_grad_finish_ard<T>), dim3(1), dim3(KUF_THREADS), 0, s, part, nblk, ndim, sig2,
+                     reinterpret_cast<T*>(grad));
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return hipFreeAsync(part, s);
+}
+
+// launcher behind hgp_kuf_grid_grad_ard: SqExp, point observations, grad holds 1 + ndim values
+hipError_t kuf_grad_ard(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
+                        double sig2, const double* ell, const void* gup, void* grad, hipStream_t s) {
+  if (dtype == HGP_F32) return kuf_grad_ard_t<float>(ndim, m, grids, x, nobs, sig2, ell, gup, grad, s);
+  return kuf_grad_ard_t<double>(ndim, m, grids, x, nobs, sig2, ell, gup, grad, s);
 }
 
 // k_semi_mc is |x_n| mean_a k(u_j, alpha_a x_n) and neither |x_n| nor alpha_a depends on the

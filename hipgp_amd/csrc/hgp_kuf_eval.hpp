@@ -17,6 +17,35 @@ struct KufGrid {
   const void* g[3];
 };
 
+// One value per axis, by value in the kernel arguments: the length scales of the point kernels
+// (SqExp divides axis a by v[a], `kernels.py:73-79` with a vector ell; Matern reads v[0] alone, its
+// one ell) and the radii of the window.  A scalar caller's value stands in all three, and then
+// every kernel forms what it formed from the one value.
+template <typename T>
+struct KufVec {
+  T v[3];
+};
+
+// v[d - 1] of a d-axis grid without a run-time index into the kernel arguments
+template <typename T>
+__host__ __device__ __forceinline__ T kuf_last(const KufVec<T>& e, int d) {
+  return d == 1 ? e.v[0] : (d == 2 ? e.v[1] : e.v[2]);
+}
+
+// v[a] likewise, a in {0, 1, 2}
+template <typename T>
+__host__ __device__ __forceinline__ T kuf_at(const KufVec<T>& e, int a) {
+  return a == 0 ? e.v[0] : (a == 1 ? e.v[1] : e.v[2]);
+}
+
+// from three host doubles, each rounded once to T
+template <typename T>
+inline KufVec<T> kuf_vec(const double* p) {
+  KufVec<T> e;
+  for (int a = 0; a < 3; ++a) e.v[a] = (T)p[a];
+  return e;
+}
+
 // s: SqExp / Gneiting -> sum ((x - y) / ell)^2 ; Matern -> sum (x - y)^2   (as the reference)
 __host__ __device__ inline bool scaled_dist(int kind) { return kind == HGP_KERN_SQEXP || kind == HGP_KERN_GNEITING; }
 

@@ -39,7 +39,8 @@ constexpr int MV_THREADS = SEMI_THREADS;   // block of the line-integral kernels
 constexpr int MV_MIN_UNITS = 4;   // nsplit = 0 leaves a slice at least this many units
 
 template <typename T, int KIND, int NW>
-__global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2, T ell,
+__global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2,
+                                                        KufVec<T> ell,
                                                         const T* __restrict__ w, int nwv, int64_t M, int nsplit,
                                                         int64_t nunit, double* __restrict__ part,
                                                         T* __restrict__ out, int64_t ldo) {
@@ -57,6 +58,7 @@ __global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __r
   T xv[3] = {0, 0, 0};
   for (int a = 0; a < d; ++a) xv[a] = x[n * d + a];
   const T xl = xv[d - 1];
+  const T ell_l = kuf_last(ell, d);                          // the last axis' length scale
   const T* g0 = reinterpret_cast<const T*>(g.g[0]);
   const T* g1 = reinterpret_cast<const T*>(g.g[d > 1 ? 1 : 0]);
   const T* gl = reinterpret_cast<const T*>(g.g[d - 1]);
@@ -74,13 +76,13 @@ __global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __r
     T so = 0;
     if (d == 2) {
       T dv = xv[0] - g0[o];
-      if (sq) dv = dv / ell;
+      if (sq) dv = dv / ell.v[0];
       so = dv * dv;
     } else if (d == 3) {
       T dv = xv[0] - g0[o / g.m[1]];
-      if (sq) dv = dv / ell;
+      if (sq) dv = dv / ell.v[0];
       T dw = xv[1] - g1[o % g.m[1]];
-      if (sq) dw = dw / ell;
+      if (sq) dw = dw / ell.v[1];
       so = dv * dv + dw * dw;
     }
     for (int64_t i0 = ia; i0 < ib; i0 += MV_RUN) {
@@ -91,9 +93,9 @@ __global__ __launch_bounds__(MV_TILE) void k_kuf_grid_mv(KufGrid g, const T* __r
 #pragma unroll 4
       for (int64_t i = i0; i < i1; ++i) {
         T dv = xl - gl[i];
-        if (sq) dv = dv / ell;
+        if (sq) dv = dv / ell_l;
         const T sv = so + dv * dv;                           // d = 1: so = 0, the same bits as dv * dv
-        const T kv = kern_eval<T>(KIND, sv, sig2, ell);
+        const T kv = kern_eval<T>(KIND, sv, sig2, ell.v[0]);
 #pragma unroll
         for (int s = 0; s < NW; ++s) run[s] += kv * wp[s][base + i];
       }
@@ -193,8 +195,10 @@ __global__ __launch_bounds__(MV_THREADS) void k_kuf_semi_mv(KufGrid g, const T* 
 // mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs > 0, nw > 0, nsplit >= 0.
 template <typename T>
 static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                               const void* xv, int64_t nobs, double sig2, double ell, int npts, const void* uv,
-                               const void* wv, int64_t nw, int64_t nsplit_in, void* outv, hipStream_t s) {
+                               const void* xv, int64_t nobs, double sig2, const double* ell3, int npts,
+                               const void* uv, const void* wv, int64_t nw, int64_t nsplit_in, void* outv,
+                               hipStream_t s) {
+  const double ell = ell3[0];                                // the line integrals' one length scale
   KufGrid g{};
   int64_t M, outer;
   kuf_fill_grid(g, ndim, m, grids, &M, &outer);
@@ -227,7 +231,8 @@ static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const in
           if (mode == 0)
             kuf_with_kind(kind, [&](auto K) {
               hipLaunchKernelGGL((k_kuf_grid_mv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(MV_TILE),
-                                 0, s, g, x, nobs, (T)sig2, (T)ell, wg, nwv, M, (int)nsplit, nunit, part, og, nw);
+                                 0, s, g, x, nobs, (T)sig2, kuf_vec<T>(ell3), wg, nwv, M, (int)nsplit, nunit, part, og,
+                                 nw);
             });
           else
             kuf_with_mode(mode, [&](auto MD) {
@@ -244,10 +249,11 @@ static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const in
       });
 }
 
-// launcher behind hgp_kuf_grid_matvec / hgp_kuf_semi_mc_matvec / hgp_kuf_semi_sqexp_matvec
+// launcher behind hgp_kuf_grid_matvec(_ard) / hgp_kuf_semi_mc_matvec / hgp_kuf_semi_sqexp_matvec; ell: one value
+// per axis, three in all (a scalar entry's value in each; the line integrals read the first)
 hipError_t kuf_matvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                      const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* w,
-                      int64_t nw, int64_t nsplit, void* out, hipStream_t s) {
+                      const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
+                      const void* w, int64_t nw, int64_t nsplit, void* out, hipStream_t s) {
   if (dtype == HGP_F32)
     return kuf_matvec_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out, s);
   return kuf_matvec_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out, s);

@@ -43,14 +43,14 @@ constexpr int RMV_RUN = 256;      // longest run summed in the tensor dtype; the
 // distance is kuf_sqdist's, with the forward's roundings spelled out.
 template <typename T, int KIND, int NC, int D>
 __device__ __forceinline__ void rmv_run(const T* __restrict__ x, int64_t r0, int64_t r1, T u0, T u1, T ul, T sig2,
-                                        T ell, const T* const (&cp)[NC], T (&run)[NC]) {
+                                        const KufVec<T>& ell, const T* const (&cp)[NC], T (&run)[NC]) {
 #pragma unroll 4
   for (int64_t n = r0; n < r1; ++n) {
-    const T d0 = D >= 2 ? kuf_axis<T, KIND>(x[n * D], u0, ell) : (T)0;
-    const T d1 = D == 3 ? kuf_axis<T, KIND>(x[n * D + 1], u1, ell) : (T)0;
-    const T dv = kuf_axis<T, KIND>(x[n * D + D - 1], ul, ell);
+    const T d0 = D >= 2 ? kuf_axis<T, KIND>(x[n * D], u0, ell.v[0]) : (T)0;
+    const T d1 = D == 3 ? kuf_axis<T, KIND>(x[n * D + 1], u1, ell.v[1]) : (T)0;
+    const T dv = kuf_axis<T, KIND>(x[n * D + D - 1], ul, ell.v[D - 1]);
     const T sv = kuf_sqdist<T>(D, d0, d1, dv);
-    const T kv = kern_eval<T>(KIND, sv, sig2, ell);
+    const T kv = kern_eval<T>(KIND, sv, sig2, ell.v[0]);
 #pragma unroll
     for (int s = 0; s < NC; ++s) run[s] += kv * cp[s][n];
   }
@@ -58,7 +58,7 @@ __device__ __forceinline__ void rmv_run(const T* __restrict__ x, int64_t r0, int
 
 template <typename T, int KIND, int NC>
 __global__ __launch_bounds__(RMV_TILE) void k_kuf_grid_rmv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2,
-                                                          T ell, const T* __restrict__ c, int ncv, int64_t M,
+                                                          KufVec<T> ell, const T* __restrict__ c, int ncv, int64_t M,
                                                           int nsplit, int64_t nrun, double* __restrict__ part,
                                                           T* __restrict__ out) {
   const int d = g.d;
@@ -230,8 +230,10 @@ __global__ __launch_bounds__(RMV_TILE) void k_kuf_semi_rmv(KufGrid g, const T* _
 // mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs >= 0, nc > 0, nsplit >= 0.
 template <typename T>
 static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                                const void* xv, int64_t nobs, double sig2, double ell, int npts, const void* uv,
-                                const void* cv, int64_t nc, int64_t nsplit_in, void* outv, hipStream_t s) {
+                                const void* xv, int64_t nobs, double sig2, const double* ell3, int npts,
+                                const void* uv, const void* cv, int64_t nc, int64_t nsplit_in, void* outv,
+                                hipStream_t s) {
+  const double ell = ell3[0];                                // the line integrals' one length scale
   KufGrid g{};
   int64_t M, outer;
   kuf_fill_grid(g, ndim, m, grids, &M, &outer);
@@ -264,7 +266,7 @@ static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const i
           if (mode == 0)
             kuf_with_kind(kind, [&](auto K) {
               hipLaunchKernelGGL((k_kuf_grid_rmv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(RMV_TILE),
-                                 0, s, g, x, nobs, (T)sig2, (T)ell, cg, ncv, M, (int)nsplit, nrun, part, og);
+                                 0, s, g, x, nobs, (T)sig2, kuf_vec<T>(ell3), cg, ncv, M, (int)nsplit, nrun, part, og);
             });
           else
             kuf_with_mode(mode, [&](auto MD) {
@@ -281,10 +283,11 @@ static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const i
       });
 }
 
-// launcher behind hgp_kuf_grid_rmatvec / hgp_kuf_semi_mc_rmatvec / hgp_kuf_semi_sqexp_rmatvec
+// launcher behind hgp_kuf_grid_rmatvec(_ard) / hgp_kuf_semi_mc_rmatvec / hgp_kuf_semi_sqexp_rmatvec; ell: one
+// value per axis, three in all (a scalar entry's value in each; the line integrals read the first)
 hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                       const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* c,
-                       int64_t nc, int64_t nsplit, void* out, hipStream_t s) {
+                       const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
+                       const void* c, int64_t nc, int64_t nsplit, void* out, hipStream_t s) {
   if (dtype == HGP_F32)
     return kuf_rmatvec_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out, s);
   return kuf_rmatvec_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out, s);

@@ -5,10 +5,12 @@
 // The dense twins (hgp_kuf_mv.hip, hgp_kuf_rmv.hip) evaluate all nobs * M kernel values; these
 // evaluate the pairs of the window alone.
 //
-// The window.  Pair (n, j) belongs to it iff fabs(x[n][a] - g_a[j_a]) <= rho on every axis a, in
-// the tensor dtype, rho rounded once to that dtype (win_in).  A box, not a ball: with rho the
+// The window.  Pair (n, j) belongs to it iff fabs(x[n][a] - g_a[j_a]) <= rho[a] on every axis a, in
+// the tensor dtype, each rho[a] rounded once to that dtype (win_in).  A box, not a ball: with rho the
 // distance from which k(r) <= tol sig2 on, every dropped pair is farther than rho and its value
-// under tol sig2.  The rounded difference x - g_a[i] does not increase with i on a strictly
+// under tol sig2.  A SqExp with one length scale per axis has one radius per axis, rho[a] the
+// distance from which axis a's factor alone is <= tol: a dropped pair has such an axis and the other
+// factors are <= 1.  The scalar entries put their one radius on every axis.  The rounded difference x - g_a[i] does not increase with i on a strictly
 // increasing axis, so per axis the box is an index range [lo, hi) and two binary searches with
 // the predicate's own comparisons find exactly the set the predicate describes (win_first).  The
 // matvec finds the ranges that way, the rmatvec applies the predicate pair by pair: one set, so
@@ -73,8 +75,8 @@ __device__ __forceinline__ int64_t win_first(const T* __restrict__ g, int64_t m,
 
 template <typename T, int KIND, int NW>
 __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_mv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2,
-                                                           T ell, T rho, const T* __restrict__ w, int nwv, int64_t M,
-                                                           T* __restrict__ out, int64_t ldo) {
+                                                           KufVec<T> ell, KufVec<T> rho, const T* __restrict__ w,
+                                                           int nwv, int64_t M, T* __restrict__ out, int64_t ldo) {
   const int d = g.d;
   const int lane = threadIdx.x & 63;
   const int64_t n = (int64_t)blockIdx.x * (WIN_THREADS / 64) + (threadIdx.x >> 6);
@@ -90,12 +92,13 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_mv(KufGrid g, const T* 
   const int q = lane < 2 * d ? lane : 0;
   const int qa = q >> 1;
   const long long r = win_first<T>(qa == 0 ? g0 : (qa == 1 ? g1 : g2), qa == 0 ? m0 : (qa == 1 ? m1 : m2),
-                                   qa == 0 ? x0 : (qa == 1 ? x1 : x2), rho, (q & 1) != 0);
+                                   qa == 0 ? x0 : (qa == 1 ? x1 : x2), kuf_at(rho, qa), (q & 1) != 0);
   const int64_t lo0 = __shfl(r, 0, 64), hi0 = __shfl(r, 1, 64);
   const int64_t lo1 = d > 1 ? __shfl(r, 2, 64) : 0, hi1 = d > 1 ? __shfl(r, 3, 64) : 0;
   const int64_t lo2 = d > 2 ? __shfl(r, 4, 64) : 0, hi2 = d > 2 ? __shfl(r, 5, 64) : 0;
   // the last axis (lanes) and up to two outer ones (rows); an absent outer axis is one row
   const T xl = d == 1 ? x0 : (d == 2 ? x1 : x2);
+  const T ell_l = kuf_last(ell, d);
   const T* gl = d == 1 ? g0 : (d == 2 ? g1 : g2);
   const int64_t inner = d == 1 ? m0 : (d == 2 ? m1 : m2);
   const int64_t loL = d == 1 ? lo0 : (d == 2 ? lo1 : lo2), hiL = d == 1 ? hi0 : (d == 2 ? hi1 : hi2);
@@ -108,17 +111,17 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_mv(KufGrid g, const T* 
 #pragma unroll
   for (int s = 0; s < NW; ++s) acc[s] = 0;
   for (int64_t o0 = a0; o0 < b0; ++o0) {
-    const T d0 = d >= 2 ? kuf_axis<T, KIND>(x0, g0[o0], ell) : (T)0;
+    const T d0 = d >= 2 ? kuf_axis<T, KIND>(x0, g0[o0], ell.v[0]) : (T)0;
     for (int64_t o1 = a1; o1 < b1; ++o1) {
-      const T d1 = d == 3 ? kuf_axis<T, KIND>(x1, g1[o1], ell) : (T)0;
+      const T d1 = d == 3 ? kuf_axis<T, KIND>(x1, g1[o1], ell.v[1]) : (T)0;
       const T so = kuf_outer<T>(d, d0, d1);
       const int64_t base = (d == 3 ? o0 * m1 + o1 : (d == 2 ? o0 : 0)) * inner;
       T run[NW];
 #pragma unroll
       for (int s = 0; s < NW; ++s) run[s] = 0;
       for (int64_t i = loL + lane; i < hiL; i += 64) {
-        const T dv = kuf_axis<T, KIND>(xl, gl[i], ell);
-        const T kv = kern_eval<T>(KIND, kuf_fma(dv, dv, so), sig2, ell);
+        const T dv = kuf_axis<T, KIND>(xl, gl[i], ell_l);
+        const T kv = kern_eval<T>(KIND, kuf_fma(dv, dv, so), sig2, ell.v[0]);
 #pragma unroll
         for (int s = 0; s < NW; ++s) run[s] += kv * wp[s][base + i];
       }
@@ -153,8 +156,8 @@ __device__ __forceinline__ int64_t win_cell(const T* __restrict__ g, int64_t m, 
 
 template <typename T, int KIND, int NC, int D>
 __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T* __restrict__ x, int64_t B, T sig2,
-                                                            T ell, T rho, const T* __restrict__ c, int ncv, int64_t M,
-                                                            const int64_t* __restrict__ order,
+                                                            KufVec<T> ell, KufVec<T> rho, const T* __restrict__ c,
+                                                            int ncv, int64_t M, const int64_t* __restrict__ order,
                                                             const int64_t* __restrict__ bin_start,
                                                             T* __restrict__ out) {
   __shared__ T xs[D][WIN_CHUNK];
@@ -180,7 +183,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
     const int64_t first = a == 0 ? tp.t0 * T0 : (a == 1 ? tp.t1 * T1 : tp.t2 * T2);
     int64_t last = first + (a == 0 ? T0 : (a == 1 ? T1 : T2)) - 1;
     if (last > ma - 1) last = ma - 1;
-    const double rw = (double)rho * (1.0 + 1e-6);
+    const double rw = (double)kuf_at(rho, a) * (1.0 + 1e-6);
     const double ge = (double)ga[(tid & 1) ? last : first];
     const double slack = 1e-15 * fabs(ge);
     cell_s[tid] = win_cell<T>(ga, ma, (tid & 1) ? ge + rw + slack : ge - rw - slack);
@@ -226,14 +229,14 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
             const T p0 = xs[0][k];
             const T p1 = D > 1 ? xs[D > 1 ? 1 : 0][k] : (T)0;
             const T p2 = D > 2 ? xs[D > 2 ? 2 : 0][k] : (T)0;
-            bool in = win_in<T>(p0, u0, rho);
-            if (D > 1) in = in && win_in<T>(p1, u1, rho);
-            if (D > 2) in = in && win_in<T>(p2, u2, rho);
+            bool in = win_in<T>(p0, u0, rho.v[0]);
+            if (D > 1) in = in && win_in<T>(p1, u1, rho.v[1]);
+            if (D > 2) in = in && win_in<T>(p2, u2, rho.v[2]);
             if (in) {
-              const T d0 = D >= 2 ? kuf_axis<T, KIND>(p0, u0, ell) : (T)0;
-              const T d1 = D == 3 ? kuf_axis<T, KIND>(p1, u1, ell) : (T)0;
-              const T dv = kuf_axis<T, KIND>(D == 1 ? p0 : (D == 2 ? p1 : p2), ul, ell);
-              const T kv = kern_eval<T>(KIND, kuf_sqdist<T>(D, d0, d1, dv), sig2, ell);
+              const T d0 = D >= 2 ? kuf_axis<T, KIND>(p0, u0, ell.v[0]) : (T)0;
+              const T d1 = D == 3 ? kuf_axis<T, KIND>(p1, u1, ell.v[1]) : (T)0;
+              const T dv = kuf_axis<T, KIND>(D == 1 ? p0 : (D == 2 ? p1 : p2), ul, ell.v[D - 1]);
+              const T kv = kern_eval<T>(KIND, kuf_sqdist<T>(D, d0, d1, dv), sig2, ell.v[0]);
 #pragma unroll
               for (int s = 0; s < NC; ++s) run[s] += kv * cs[s][k];
             }
@@ -254,8 +257,8 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
 // nobs > 0, nw > 0
 template <typename T>
 static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const void* const* grids, const void* xv,
-                                   int64_t nobs, double sig2, double ell, double rho, const void* wv, int64_t nw,
-                                   void* outv, hipStream_t s) {
+                                   int64_t nobs, double sig2, const double* ell, const double* rho, const void* wv,
+                                   int64_t nw, void* outv, hipStream_t s) {
   KufGrid g{};
   int64_t M;
   kuf_fill_grid(g, ndim, m, grids, &M);
@@ -270,7 +273,7 @@ static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const v
     kuf_with_kind(kind, [&](auto K) {
       kuf_with_width(NW, [&](auto W) {
         hipLaunchKernelGGL((k_kuf_win_mv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(WIN_THREADS), 0,
-                           s, g, x, nobs, (T)sig2, (T)ell, (T)rho, w + s0 * M, nwv, M, out + s0, nw);
+                           s, g, x, nobs, (T)sig2, kuf_vec<T>(ell), kuf_vec<T>(rho), w + s0 * M, nwv, M, out + s0, nw);
       });
     });
   });
@@ -279,8 +282,9 @@ static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const v
 // nobs >= 0 (0: out zeroed), nc > 0
 template <typename T>
 static hipError_t kuf_rmatvec_win_t(int kind, int ndim, const int64_t* m, const void* const* grids, const void* xv,
-                                    int64_t nobs, double sig2, double ell, double rho, const void* cv, int64_t nc,
-                                    const int64_t* order, const int64_t* bin_start, void* outv, hipStream_t s) {
+                                    int64_t nobs, double sig2, const double* ell, const double* rho, const void* cv,
+                                    int64_t nc, const int64_t* order, const int64_t* bin_start, void* outv,
+                                    hipStream_t s) {
   KufGrid g{};
   int64_t M;
   kuf_fill_grid(g, ndim, m, grids, &M);
@@ -296,26 +300,27 @@ static hipError_t kuf_rmatvec_win_t(int kind, int ndim, const int64_t* m, const 
       kuf_with_dim(ndim, [&](auto D) {
         kuf_with_width(NC, [&](auto W) {
           hipLaunchKernelGGL((k_kuf_win_rmv<T, decltype(K)::value, decltype(W)::value, decltype(D)::value>), dim3(nb),
-                             dim3(WIN_THREADS), 0, s, g, x, nobs, (T)sig2, (T)ell, (T)rho, c + s0 * nobs, ncv, M,
-                             order, bin_start, out + s0 * M);
+                             dim3(WIN_THREADS), 0, s, g, x, nobs, (T)sig2, kuf_vec<T>(ell), kuf_vec<T>(rho),
+                             c + s0 * nobs, ncv, M, order, bin_start, out + s0 * M);
         });
       });
     });
   });
 }
 
-// launcher behind hgp_kuf_grid_matvec_win
+// launcher behind hgp_kuf_grid_matvec_win(_ard); ell, rho: one value per axis, three each (a scalar entry's value
+// in each)
 hipError_t kuf_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                          int64_t nobs, double sig2, double ell, double rho, const void* w, int64_t nw, void* out,
-                          hipStream_t s) {
+                          int64_t nobs, double sig2, const double* ell, const double* rho, const void* w, int64_t nw,
+                          void* out, hipStream_t s) {
   if (dtype == HGP_F32)
     return kuf_matvec_win_t<float>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, w, nw, out, s);
   return kuf_matvec_win_t<double>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, w, nw, out, s);
 }
 
-// launcher behind hgp_kuf_grid_rmatvec_win
+// launcher behind hgp_kuf_grid_rmatvec_win(_ard); ell, rho as kuf_matvec_win
 hipError_t kuf_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                           int64_t nobs, double sig2, double ell, double rho, const void* c, int64_t nc,
+                           int64_t nobs, double sig2, const double* ell, const double* rho, const void* c, int64_t nc,
                            const int64_t* order, const int64_t* bin_start, void* out, hipStream_t s) {
   if (dtype == HGP_F32)
     return kuf_rmatvec_win_t<float>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, c, nc, order, bin_start, out, s);

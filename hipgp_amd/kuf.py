@@ -5,7 +5,12 @@ observations (hgp_kuf_semi_mc / hgp_kuf_semi_sqexp / hgp_knn_doubly_diag).
 (B, M, D) broadcast of `kernels.py:78,149`; this computes the same values with one fused HIP
 kernel straight into the (B, M) layout the PCG reads.  Used when the kernel is SqExp or
 Matern(nu in {1/2, 3/2, 5/2}) with a scalar length scale and no gradient is needed; other
-kernels (or kernel-hyper-parameter learning) evaluate the torch kernel on the device.
+kernels (or kernel-hyper-parameter learning) evaluate the torch kernel on the device.  A SqExp
+declared with `ard=True` also takes one length scale per axis for point observations
+(`kernels.py:73-79`: ell "a scalar, or a tensor that matches the dimension of data"), through the
+hgp_kuf_grid*_ard entries: `kuf_grid`, the two products, their windowed twins (one radius per axis)
+and `kuf_grid_ad`.  Without that declaration a vector ell is declined as before, and the
+line-integral functions decline it always.
 
 Kernel-hyper-parameter learning has fused twins, `kuf_grid_ad` / `kuf_semi_mc_ad` /
 `kuf_semi_sqexp_ad`: the same forward, and the gradient with respect to (sig2, ell) by
@@ -54,6 +59,36 @@ def _scalar(v):
     return float(v)
 
 
+def _ell_arg(v, D):
+    """ell as the fused kernels take it: a float for a scalar (number, or tensor of one element), a
+    list of D floats for a 1-D tensor or sequence of length D (one length scale per axis), else None."""
+    if torch.is_tensor(v):
+        if v.numel() == 1:
+            return _scalar(v)
+        if v.dim() == 1 and v.numel() == D:
+            return [float(e) for e in v.detach().cpu().tolist()]
+        return None
+    if isinstance(v, (list, tuple)):
+        return [float(e) for e in v] if len(v) == D else None
+    return float(v)
+
+
+def _is_ard(el):
+    return isinstance(el, list)
+
+
+def _takes_ard(kernel):
+    """True for a SqExp declared with one length scale per axis (`SqExp(ard=True)`): the only kernel
+    for which a vector ell is read as per-axis scales; every other kernel declines a vector."""
+    from hipgp_amd.ziggy import kernels as zk
+    return isinstance(kernel, zk.SqExp) and bool(getattr(kernel, "ard", False))
+
+
+def _dvec(vals):
+    """host doubles for a `const double*` argument"""
+    return (ctypes.c_double * len(vals))(*vals)
+
+
 def kuf_grid(kernel, xgrids, x, params):
     """Knm (nobs, M) for observations x (nobs, D) against the C-order mesh of xgrids, or None
     when the fused path does not apply (caller then evaluates the torch kernel)."""
@@ -65,8 +100,8 @@ def kuf_grid(kernel, xgrids, x, params):
     sig2, ell = params
     if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in (sig2, ell, x)):
         return None
-    s2, el = _scalar(sig2), _scalar(ell)
-    if s2 is None or el is None:
+    s2, el = _scalar(sig2), _ell_arg(ell, len(xgrids))
+    if s2 is None or el is None or (_is_ard(el) and not _takes_ard(kernel)):
         return None
     grids = [g.to(device=x.device, dtype=x.dtype).contiguous() for g in xgrids]
     xc = x.detach().contiguous()
@@ -76,13 +111,20 @@ def kuf_grid(kernel, xgrids, x, params):
     out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
     m = (ctypes.c_int64 * len(grids))(*[g.numel() for g in grids])
     ptrs = (ctypes.c_void_p * len(grids))(*[g.data_ptr() for g in grids])
+    if _is_ard(el):
+        check(lib().hgp_kuf_grid_ard(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
+                                     ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, _dvec(el),
+                                     ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+        return out
     check(lib().hgp_kuf_grid(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
                              x.shape[0], s2, el, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
     return out
 
 
-def _grid_call_args(kernel, xgrids, x, params, gneiting=False):
-    """(kind, s2, el, grids, xc, M) for the fused grid kernels, or None when they do not apply."""
+def _grid_call_args(kernel, xgrids, x, params, gneiting=False, ard=False):
+    """(kind, s2, el, grids, xc, M) for the fused grid kernels, or None when they do not apply.  el is
+    a float; with `ard` (the point functions) a list of one float per axis for a vector ell, which
+    a SqExp declared with ard=True alone takes."""
     kind = kernel_kind(kernel, gneiting=gneiting)
     if kind is None or x.device.type != "cuda" or x.dim() != 2 or x.shape[1] != len(xgrids):
         return None
@@ -91,8 +133,10 @@ def _grid_call_args(kernel, xgrids, x, params, gneiting=False):
     sig2, ell = params
     if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in (sig2, ell, x)):
         return None
-    s2, el = _scalar(sig2), _scalar(ell)
+    s2, el = _scalar(sig2), _ell_arg(ell, len(xgrids))
     if s2 is None or el is None:
+        return None
+    if _is_ard(el) and not (ard and _takes_ard(kernel)):
         return None
     grids = [g.to(device=x.device, dtype=x.dtype).contiguous() for g in xgrids]
     M = 1
@@ -162,7 +206,7 @@ def kuf_grid_matvec(kernel, xgrids, x, params, W, nsplit=0):
     """kuf_grid(...) @ W^T as an (nobs, nw) tensor without the (nobs, M) matrix
     (hgp_kuf_grid_matvec): W is (nw, M) or (M,).  nsplit: slices of the grid summed apart (0: the
     library's choice).  None under the rules by which `kuf_grid` declines."""
-    a = _grid_call_args(kernel, xgrids, x, params)
+    a = _grid_call_args(kernel, xgrids, x, params, ard=True)
     if a is None:
         return None
     kind, s2, el, grids, xc, M = a
@@ -171,6 +215,12 @@ def kuf_grid_matvec(kernel, xgrids, x, params, W, nsplit=0):
         return None
     out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
     m, ptrs = _grid_ptrs(grids)
+    if _is_ard(el):
+        check(lib().hgp_kuf_grid_matvec_ard(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
+                                            ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, _dvec(el),
+                                            ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
+                                            ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+        return out
     check(lib().hgp_kuf_grid_matvec(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
                                     x.shape[0], s2, el, ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
                                     ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
@@ -239,7 +289,7 @@ def kuf_grid_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
     """C @ kuf_grid(...) as an (nc, M) tensor without the (nobs, M) matrix (hgp_kuf_grid_rmatvec):
     C is (nc, nobs) or (nobs,).  nsplit: slices of the observations summed apart (0: the library's
     choice).  None under the rules by which `kuf_grid` declines."""
-    a = _grid_call_args(kernel, xgrids, x, params)
+    a = _grid_call_args(kernel, xgrids, x, params, ard=True)
     if a is None:
         return None
     kind, s2, el, grids, xc, M = a
@@ -248,6 +298,12 @@ def kuf_grid_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
         return None
     out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
     m, ptrs = _grid_ptrs(grids)
+    if _is_ard(el):
+        check(lib().hgp_kuf_grid_rmatvec_ard(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
+                                             ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, _dvec(el),
+                                             ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
+                                             ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+        return out
     check(lib().hgp_kuf_grid_rmatvec(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
                                      ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el,
                                      ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
@@ -322,10 +378,17 @@ def _kern_unit64(kind, r, el):
 
 def support_radius(kernel, params, tol):
     """The smallest distance rho (a float, fp64) with k(r) <= tol * sig2 for every r >= rho, or
-    None where no rule applies: Gneiting or a kernel without a fused forward, a vector `ell`, `tol`
-    outside (0, 1).  SqExp in closed form, ell * sqrt(2 ln(1 / tol)) (moved up by at most a few ulps
-    so that the fp64 formula itself is <= tol there); Matern 1/2, 3/2, 5/2, all decreasing in r, by
-    bisection on the fp64 formula."""
+    None where no rule applies: Gneiting or a kernel without a fused forward, a vector `ell` with
+    a kernel other than a SqExp declared with ard=True, `tol` outside (0, 1).  SqExp in closed form, ell * sqrt(2 ln(1 / tol))
+    (moved up by at most a few ulps so that the fp64 formula itself is <= tol there); Matern 1/2, 3/2,
+    5/2, all decreasing in r, by bisection on the fp64 formula.
+
+    `SqExp(ard=True)` with a vector `ell` (a 1-D tensor or a sequence, one length scale per axis): a list,
+    rho[a] = ell[a] * sqrt(2 ln(1 / tol)), each moved up as the scalar is, so that axis a's factor
+    exp(-(rho[a] / ell[a])^2 / 2) alone is <= tol.  The window is then the box |x_a - u_a| <= rho[a]
+    on every axis, and the bound is the scalar one: a pair outside has an axis with
+    (d_a / ell[a])^2 > 2 ln(1 / tol), the other factors are <= 1, hence k < tol * sig2, and a
+    windowed product is within tol * sig2 * sum |w| of the dense one per output."""
     import math
     kind = kernel_kind(kernel)
     if kind is None or tol is None:
@@ -334,6 +397,13 @@ def support_radius(kernel, params, tol):
     if not (0. < tol < 1.):
         return None
     sig2, ell = params
+    if torch.is_tensor(ell) and ell.numel() != 1 or isinstance(ell, (list, tuple)):
+        el = _ell_arg(ell, ell.numel() if torch.is_tensor(ell) else len(ell))
+        if not _takes_ard(kernel) or _scalar(sig2) is None or not _is_ard(el):
+            return None
+        if not all(e > 0 and math.isfinite(e) for e in el):
+            return None
+        return [support_radius(kernel, (sig2, e), tol) for e in el]
     s2, el = _scalar(sig2), _scalar(ell)
     if s2 is None or el is None or not (el > 0) or not math.isfinite(el):
         return None
@@ -376,19 +446,27 @@ class WindowPlan:
     are read here and must not change while the plan is in use.
 
     Pair (n, j) is in the window iff |x[n, a] - g_a[j_a]| <= rho on every axis a, evaluated in
-    x's dtype with rho rounded once to that dtype.  The constructor raises ValueError where the
-    windowed products do not apply; `WindowPlan.make` returns None there instead."""
+    x's dtype with rho rounded once to that dtype.  `SqExp(ard=True)` with a vector ell: `ell` and `rho` are
+    lists, one value per axis, and the predicate reads rho[a] on axis a (a scalar `rho` given with a
+    vector ell stands on every axis).  The constructor raises ValueError where the windowed products
+    do not apply; `WindowPlan.make` returns None there instead."""
 
     def __init__(self, kernel, xgrids, x, params, tol, rho=None):
-        a = _grid_call_args(kernel, xgrids, x, params)
+        a = _grid_call_args(kernel, xgrids, x, params, ard=True)
         if rho is None:
             rho = support_radius(kernel, params, tol)
-        if a is None or rho is None or not (float(rho) >= 0) or float(rho) == float("inf"):
+        if a is not None and rho is not None and _is_ard(a[2]):
+            rho = [float(r) for r in rho] if isinstance(rho, (list, tuple)) else [float(rho)] * len(a[2])
+            ok = len(rho) == len(a[2]) and all(r >= 0 and r != float("inf") for r in rho)
+        else:
+            ok = a is not None and rho is not None and not isinstance(rho, (list, tuple)) and \
+                float(rho) >= 0 and float(rho) != float("inf")
+        if not ok:
             raise ValueError("the windowed Kuf products do not apply: they take SqExp / Matern(1/2, 3/2, 5/2) with a "
-                             "scalar ell, a tolerance in (0, 1), device points (nobs, D <= 3) in fp32 / fp64 and no "
-                             "graph to x, sig2 or ell")
+                             "scalar ell (SqExp(ard=True) also one ell per axis), a tolerance in (0, 1), device points "
+                             "(nobs, D <= 3) in fp32 / fp64 and no graph to x, sig2 or ell")
         self.kind, self.sig2, self.ell, self.grids, self.x, self.M = a
-        self.rho, self.tol = float(rho), tol
+        self.rho, self.tol = rho if _is_ard(self.ell) else float(rho), tol
         self.dims = [g.numel() for g in self.grids]
         self._bins = None
 
@@ -433,6 +511,12 @@ def kuf_grid_matvec_win(plan, W):
         return None
     out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
     m, ptrs = _grid_ptrs(plan.grids)
+    if _is_ard(plan.ell):
+        check(lib().hgp_kuf_grid_matvec_win_ard(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
+                                                ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, _dvec(plan.ell),
+                                                _dvec(plan.rho), ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0],
+                                                ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+        return out
     check(lib().hgp_kuf_grid_matvec_win(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
                                         ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho,
                                         ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], ctypes.c_void_p(out.data_ptr()),
@@ -453,6 +537,13 @@ def kuf_grid_rmatvec_win(plan, C):
     order, start = plan.bins() if x.shape[0] > 0 else (None, None)
     m, ptrs = _grid_ptrs(plan.grids)
     ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
+    if _is_ard(plan.ell):
+        check(lib().hgp_kuf_grid_rmatvec_win_ard(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
+                                                 ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2,
+                                                 _dvec(plan.ell), _dvec(plan.rho), ctypes.c_void_p(Cc.data_ptr()),
+                                                 Cc.shape[0], ptr(order), ptr(start),
+                                                 ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
+        return out
     check(lib().hgp_kuf_grid_rmatvec_win(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
                                          ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho,
                                          ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], ptr(order), ptr(start),
@@ -488,7 +579,7 @@ class LineWindowPlan:
 
     def __init__(self, kernel, xgrids, x, params, tol, rho=None):
         a = _grid_call_args(kernel, xgrids, x, params) if torch.is_tensor(x) and xgrids is not None else None
-        if rho is None:
+        if rho is None and a is not None:
             rho = support_radius(kernel, params, tol)
         if a is None or rho is None or not (float(rho) >= 0) or float(rho) == float("inf"):
             raise ValueError("the windowed line-integral Kuf products do not apply: they take SqExp / Matern(1/2, "
@@ -604,11 +695,14 @@ def knn_doubly_diag(table, x, params):
 class _KufAD(torch.autograd.Function):
     """out = fwd(sig2, ell) (the plain fused forward on the detached scalars); the backward hands
     the upstream gradient to bwd(sig2, ell, G) -> grad2 = (sum G dK/dsig2, sum G dK/dell).  Only
-    the detached scalars are kept on ctx; x, the grids and the MC offset live in the closures."""
+    the detached scalars are kept on ctx; x, the grids and the MC offset live in the closures.
+    A vector ell (`kuf_grid_ad` with SqExp) is kept as a list of floats and bwd returns
+    (sum G dK/dsig2, sum G dK/dell_a per axis); the ell gradient then has ell's shape."""
 
     @staticmethod
     def forward(ctx, sig2, ell, fwd, bwd):
-        ctx.s2, ctx.el, ctx.bwd = _scalar(sig2), _scalar(ell), bwd
+        ctx.s2, ctx.bwd = _scalar(sig2), bwd
+        ctx.el = _ell_arg(ell, ell.numel() if torch.is_tensor(ell) else len(ell) if isinstance(ell, (list, tuple)) else 1)
         ctx.like = [(p.shape, p.dtype) if torch.is_tensor(p) else None for p in (sig2, ell)]
         return fwd(ctx.s2, ctx.el)
 
@@ -616,14 +710,17 @@ class _KufAD(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, G):
         grad2 = ctx.bwd(ctx.s2, ctx.el, G.contiguous())
-        out = [grad2[i].to(ctx.like[i][1]).reshape(ctx.like[i][0]) if ctx.needs_input_grad[i] else None
+        parts = (grad2[:1], grad2[1:])
+        out = [parts[i].to(ctx.like[i][1]).reshape(ctx.like[i][0]) if ctx.needs_input_grad[i] else None
                for i in range(2)]
         return out[0], out[1], None, None
 
 
-def _ad_route(kernel, xgrids, x, params):
+def _ad_route(kernel, xgrids, x, params, ard=False):
     """None: the `_ad` function declines (caller evaluates the torch kernel); False: no
-    hyper-parameter gradient is asked for (the plain forward serves); else the HGP_KERN_* code."""
+    hyper-parameter gradient is asked for (the plain forward serves); else the HGP_KERN_* code.
+    ard: a 1-D ell tensor with one entry per axis passes for a SqExp declared with ard=True (the point
+    function alone)."""
     if xgrids is None or not torch.is_tensor(x) or x.requires_grad and torch.is_grad_enabled():
         return None
     kind = kernel_kind(kernel)                       # no Gneiting: its gradient is NaN at r = 0
@@ -631,16 +728,20 @@ def _ad_route(kernel, xgrids, x, params):
         return None
     if x.dtype not in (torch.float32, torch.float64) or len(xgrids) > 3:
         return None
-    if any(torch.is_tensor(p) and p.numel() != 1 for p in params):
+    sig2, ell = params
+    if torch.is_tensor(sig2) and sig2.numel() != 1:
+        return None
+    if torch.is_tensor(ell) and ell.numel() != 1 and \
+            not (ard and _takes_ard(kernel) and ell.dim() == 1 and ell.numel() == len(xgrids)):
         return None
     if not (torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in params)):
         return False
     return kind
 
 
-def _grad_call(entry, x, G, *args):
-    """Run one hgp_kuf_*_grad entry: args are everything between dtype and g."""
-    grad2 = torch.empty(2, dtype=x.dtype, device=x.device)
+def _grad_call(entry, x, G, *args, nsum=2):
+    """Run one hgp_kuf_*_grad entry: args are everything between dtype and g; nsum values come back."""
+    grad2 = torch.empty(nsum, dtype=x.dtype, device=x.device)
     check(entry(_lib.dtype_code(x.dtype), *args, ctypes.c_void_p(G.data_ptr()), ctypes.c_void_p(grad2.data_ptr()),
                 _lib.stream_ptr(x.device)))
     return grad2
@@ -653,9 +754,11 @@ def _ad_inputs(xgrids, x):
 
 def kuf_grid_ad(kernel, xgrids, x, params):
     """`kuf_grid` that carries the autograd graph to sig2 / ell: the same forward values, the
-    backward by hgp_kuf_grid_grad.  None when it does not apply: x requires grad, a non-scalar
-    ell, Gneiting or another kernel without a fused forward, a CPU tensor, more than 3 dims."""
-    kind = _ad_route(kernel, xgrids, x, params)
+    backward by hgp_kuf_grid_grad.  `SqExp(ard=True)` also with a 1-D ell of one entry per axis (backward by
+    hgp_kuf_grid_grad_ard; the ell gradient has ell's shape).  None when it does not apply: x requires
+    grad, any other non-scalar ell, Gneiting or another kernel without a fused forward, a CPU tensor,
+    more than 3 dims."""
+    kind = _ad_route(kernel, xgrids, x, params, ard=True)
     if kind is None:
         return None
     if kind is False:
@@ -664,6 +767,9 @@ def kuf_grid_ad(kernel, xgrids, x, params):
 
     def bwd(s2, el, G):
         m, ptrs = _grid_ptrs(grids)
+        if _is_ard(el):
+            return _grad_call(lib().hgp_kuf_grid_grad_ard, xc, G, kind, len(grids), m, ptrs,
+                              ctypes.c_void_p(xc.data_ptr()), xc.shape[0], s2, _dvec(el), nsum=1 + len(el))
         return _grad_call(lib().hgp_kuf_grid_grad, xc, G, kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
                           xc.shape[0], s2, el)
     return _KufAD.apply(params[0], params[1], lambda s2, el: kuf_grid(kernel, grids, xc, (s2, el)), bwd)

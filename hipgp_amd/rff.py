@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .kuf import _grid_ptrs, _scalar
+from .kuf import _ell_arg, _grid_ptrs, _takes_ard
 
 TWO_PI = 2 * math.pi
 
@@ -28,23 +28,27 @@ def spectral_features(kernel, params, ndim, nfeat, generator=None, device=None, 
     """(omega (nfeat, ndim), phase (nfeat)) in radians for kernel(params): omega from the spectral
     density of the kernel as `hipgp_amd/ziggy/kernels.py` parametrises it, phase ~ U[0, 2 pi).
 
-    SqExp: omega ~ N(0, I / ell^2).  Matern nu in {1/2, 3/2, 5/2}: the multivariate t with 2 nu
+    SqExp: omega ~ N(0, I / ell^2); declared with ard=True and given one ell per axis (a 1-D tensor or sequence of ndim values,
+    `kernels.py:73-79`) omega_a ~ N(0, 1 / ell_a^2), the same normal draws divided axis by axis.  Matern nu in {1/2, 3/2, 5/2}: the multivariate t with 2 nu
     degrees of freedom, omega = z / ell * sqrt(2 nu / chi2_{2 nu}) with z ~ N(0, I) (the chi-square
     as the sum of 2 nu squared normals).  Drawn in fp64 with `generator` (on its device; the
     default generator of the CPU when None), then moved to `device` and rounded to `dtype`.
-    Gneiting (no closed-form sampler of its spectrum) and a non-scalar ell raise."""
+    Gneiting (no closed-form sampler of its spectrum), a vector ell with Matern and any other
+    non-scalar ell raise."""
     from hipgp_amd.ziggy import kernels as zk
     name = type(kernel).__name__
     if not isinstance(kernel, (zk.SqExp, zk.Matern)):
         raise NotImplementedError(f"spectral_features: no spectral sampler for the {name} kernel "
                                   "(SqExp and Matern nu in {1/2, 3/2, 5/2} only)")
-    ell = _scalar(params[1])
-    if ell is None:
-        raise NotImplementedError(f"spectral_features: the {name} kernel needs a scalar ell (no ARD)")
     ndim, nfeat = int(ndim), int(nfeat)
+    ell = _ell_arg(params[1], ndim)
+    if ell is None or (isinstance(ell, list) and not _takes_ard(kernel)):
+        raise NotImplementedError(f"spectral_features: the {name} kernel needs a scalar ell (SqExp(ard=True) also "
+                                  f"takes one ell per axis, {ndim} values)")
     gdev = generator.device if generator is not None else torch.device("cpu")
     kw = dict(generator=generator, dtype=torch.float64, device=gdev)
-    omega = torch.randn((nfeat, ndim), **kw) / ell
+    omega = torch.randn((nfeat, ndim), **kw)
+    omega = omega / (torch.tensor(ell, dtype=torch.float64, device=gdev) if isinstance(ell, list) else ell)
     if isinstance(kernel, zk.Matern):
         dof = int(round(2 * kernel.nu))
         chi2 = torch.sum(torch.randn((nfeat, dof), **kw) ** 2, dim=1, keepdim=True)

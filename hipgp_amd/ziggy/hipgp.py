@@ -67,13 +67,17 @@ class ToeplitzInducingGP(SviGP):
         self.dtype = dtype
         self.kernel = kernel
         self.N = num_obs
-        self.ell = torch.tensor(ell_init, dtype=dtype)
+        # ell_init: a float, or one positive float per axis (SqExp alone: `kernels.py:73-79` takes ell
+        # "a scalar, or a tensor that matches the dimension of data"); self.ell and log_ell are then (D,)
+        self.ell = self._ell_tensor(ell_init, kernel, len(xgrids), dtype)
         self.sig2 = torch.tensor(sig2_init, dtype=dtype)
         self.noise2 = torch.tensor(noise2_init, dtype=dtype)
         self.log_ell = nn.Parameter(torch.log(self.ell.clone()), requires_grad=learn_kernel)
         self.log_sig2 = nn.Parameter(torch.log(self.sig2.clone()), requires_grad=learn_kernel)
         self.log_noise2 = nn.Parameter(torch.log(self.noise2.clone()), requires_grad=learn_noise)
-        print(f"Model initialization: sig2 = {sig2_init:.2f}, ell_init = {ell_init:.2f}, noise2 = {noise2_init:.2f}")
+        ell_txt = f"{float(self.ell):.2f}" if self.ell.dim() == 0 else \
+            "(" + ", ".join(f"{float(e):.2f}" for e in self.ell) + ")"
+        print(f"Model initialization: sig2 = {sig2_init:.2f}, ell_init = {ell_txt}, noise2 = {noise2_init:.2f}")
         self.xgrids = xgrids
         mesh = torch.meshgrid(*xgrids, indexing="ij")
         self.xinduce = torch.stack([g.reshape(-1) for g in mesh], dim=-1)
@@ -97,7 +101,44 @@ class ToeplitzInducingGP(SviGP):
         self.xinduce = self.xinduce.to(device)
         self.kernel = self.kernel.to(device)
         self.xgrids = [g.to(device) for g in self.xgrids]
+        if self._ard():      # a (D,) ell divides device tensors (a 0-d one may stay on the host, as it always has)
+            self.ell = self.ell.to(device)
         return self
+
+    @staticmethod
+    def _ell_tensor(ell, kernel, ndim, dtype, device=None):
+        """ell as the model keeps it: a 0-d tensor for a scalar, a (D,) tensor for one length scale per
+        axis.  ValueError for a vector with a kernel other than SqExp, of the wrong length or with an
+        entry that is not positive.  A valid vector declares the kernel per-axis (`SqExp.ard = True`), which
+        is what lets the fused routes of `hipgp_amd.kuf` / `hipgp_amd.rff` read it as per-axis scales."""
+        if torch.is_tensor(ell):
+            t = ell.detach().to(dtype=dtype, device=device)
+        else:
+            t = torch.tensor(ell, dtype=dtype, device=device)
+        if t.dim() == 0:
+            return t
+        from . import kernels as zk
+        if not isinstance(kernel, zk.SqExp):
+            raise ValueError(f"one length scale per axis is defined for the SqExp kernel only, not {type(kernel).__name__} "
+                             "(the Matern formula has no vector ell)")
+        if t.dim() != 1 or t.numel() != ndim:
+            raise ValueError(f"ell must be a scalar or hold one value per grid axis ({ndim}), got shape {tuple(t.shape)}")
+        if not bool(torch.all(t > 0)) or not bool(torch.all(torch.isfinite(t))):
+            raise ValueError(f"every length scale must be positive and finite, got {t.tolist()}")
+        kernel.ard = True
+        return t
+
+    def _ard(self):
+        """True when the kernel has one length scale per axis."""
+        return self.ell.dim() > 0
+
+    _NO_ARD_LINES = ("integrated_obs=True with one length scale per axis: the line-integral cross covariances and "
+                     "the doubly-integrated diagonal table are functions of |x / ell| for ONE ell; use a scalar ell "
+                     "for line-integral observations")
+
+    def _check_ard_lines(self, integrated_obs):
+        if integrated_obs and self._ard():
+            raise NotImplementedError(self._NO_ARD_LINES)
 
     def get_kernel_params(self):
         if not self.learn_kernel:
@@ -109,7 +150,9 @@ class ToeplitzInducingGP(SviGP):
         if sig2 is not None:
             self.sig2 = torch.tensor(sig2, dtype=self.dtype, device=self.sig2.device)
         if ell is not None:
-            self.ell = torch.tensor(ell, dtype=self.dtype, device=self.ell.device)
+            self.ell = self._ell_tensor(ell, self.kernel, len(self.xgrids), self.dtype, self.ell.device)
+            if self._ard():
+                self.ell = self.ell.to(self.xgrids[0].device)
 
     def noise_terms(self, noise_std_batch):
         """(1/sigma_n^2, log sigma_n): per observation or from log_noise2 (`hipgp.py:227-230,394-399`)."""
@@ -527,6 +570,7 @@ class ToeplitzInducingGP(SviGP):
         pieces of `batch_size` points (None: a piece whose Knm stays under 256 MiB) -- every kernel,
         the "numerical" estimator and CPU stand-ins take that route."""
         from hipgp_amd import kuf
+        self._check_ard_lines(integrated_obs)
         params = self.get_kernel_params()
         out = None
         plan = None if integrated_obs else self._window_plan(x, params)
@@ -569,6 +613,7 @@ class ToeplitzInducingGP(SviGP):
         integrated_obs=True a tolerance raises NotImplementedError."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        self._check_ard_lines(integrated_obs)
         with torch.no_grad(), self._windowed(None, integrated_obs), self._line_windowed(integrated_obs):
             x = x.to(self.xgrids[0].device)
             if weights is None:
@@ -592,6 +637,7 @@ class ToeplitzInducingGP(SviGP):
         else the sum of `C[:, piece] @ _make_grams(piece)[0]` over pieces of `batch_size`
         observations (None: a piece whose Knm stays under 256 MiB)."""
         from hipgp_amd import kuf
+        self._check_ard_lines(integrated_obs)
         params = self.get_kernel_params()
         out = None
         plan = None if integrated_obs else self._window_plan(x, params)
@@ -654,6 +700,7 @@ class ToeplitzInducingGP(SviGP):
         raises NotImplementedError."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        self._check_ard_lines(integrated_obs)
         with torch.no_grad(), self._windowed(None, integrated_obs), self._line_windowed(integrated_obs):
             dev = self.xgrids[0].device
             if Kmm is None:
@@ -758,6 +805,7 @@ class ToeplitzInducingGP(SviGP):
         `predict_mean`."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        self._check_ard_lines(integrated_obs)
         with torch.no_grad(), self._windowed(None, integrated_obs), self._line_windowed(integrated_obs):
             x = x.to(self.xgrids[0].device)
             v = self.variational_draws(n, eps=eps, generator=generator)
@@ -835,7 +883,8 @@ class ToeplitzInducingGP(SviGP):
         `hipgp_amd.rff.spectral_features` returns them, prior_w (n, F) and nugget_eps (n, M)
         standard normal.  What is not given is drawn with `generator`.  Point observations and
         whitened_type='ziggy' only (integrated_obs=True raises: the feature prior is a prior of point
-        values); SqExp and Matern kernels with a scalar ell (no Gneiting, no ARD).
+        values); SqExp and Matern kernels with a scalar ell, SqExp also with one ell per axis (no
+        Gneiting).
 
         support_tol (None: the model's `kuf_support_tol`, else env HGP_KUF_SUPPORT_TOL) windows the
         Kuf product alone, as in `predict_mean`; the feature products are unchanged."""
@@ -921,9 +970,10 @@ class ToeplitzInducingGP(SviGP):
 
         Random inputs (eps, features, prior_w, nugget_eps, generator) and the one shared feature
         set per call as in `predict_samples`.  whitened_type='ziggy' only; SqExp and Matern kernels
-        with a scalar ell (no Gneiting, no ARD)."""
+        with a scalar ell (no Gneiting, no ARD: one ell per axis raises NotImplementedError)."""
         if self.whitened_type != 'ziggy':
             raise NotImplementedError(self._NO_MEAN_WEIGHTS)
+        self._check_ard_lines(True)
         from hipgp_amd import rff
         with torch.no_grad(), self._line_windowed():
             dev = self.xgrids[0].device

@@ -115,11 +115,15 @@ class Kernel(nn.Module):
 
 
 class SqExp(Kernel):
-    """`kernels.py:64-93`."""
+    """`kernels.py:64-93`.  ard=True declares one length scale per axis (`kernels.py:73-79`: ell "a scalar, or
+    a tensor that matches the dimension of data"): only then do the fused routes of `hipgp_amd.kuf` and
+    `hipgp_amd.rff` read a 1-D ell as per-axis scales; without it they decline a vector ell as they always have.
+    `ToeplitzInducingGP` sets it when it is given a vector `ell_init`.  `forward` broadcasts either way."""
 
-    def __init__(self, dtype=torch.double, Ndiag=50, dmax=5):
+    def __init__(self, dtype=torch.double, Ndiag=50, dmax=5, ard=False):
         super().__init__()
         self.dtype = dtype
+        self.ard = bool(ard)
         self.Ndiag, self.dmax = Ndiag, dmax
         self.has_k_semi = True
 

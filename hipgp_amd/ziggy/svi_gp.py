@@ -115,9 +115,14 @@ class SviGP(nn.Module):
         functions of `hipgp_amd.kuf` are tried first: the same fused forward, and a backward of two
         scalar sums that recomputes K (hgp_kuf_*_grad), so Knm is the only (B, M) array; for
         line-integral observations Knn_diag then carries its graph too (`knn_doubly_diag_ad`).
-        Where an `_ad` function does not apply (Gneiting, a non-scalar ell, no grid, ...) the torch
-        kernel is evaluated as before."""
+        Where an `_ad` function does not apply (Gneiting, no grid, ...) the torch kernel is evaluated
+        as before.  SqExp with one length scale per axis (ell of shape (D,)) takes the same fused
+        routes for point observations; integrated_obs=True then raises NotImplementedError."""
         params = self.get_kernel_params()
+        if integrated_obs and torch.is_tensor(params[1]) and params[1].dim() > 0 and params[1].numel() > 1:
+            raise NotImplementedError("integrated_obs=True with one length scale per axis: the line-integral cross "
+                                      "covariances and the doubly-integrated diagonal table are functions of "
+                                      "|x / ell| for ONE ell; use a scalar ell for line-integral observations")
         grids, xinduce = getattr(self, "xgrids", None), self.xinduce
         if grid_rows is not None:
             a, b = grid_rows
@@ -434,11 +439,15 @@ def svigp_fit(mod, odir, xtrain, ytrain, noise_std_train, xtest, ftest, etest, x
                 msg = ' ... [{}/{} ({:.0f}%)] ELBO: {:.4f}'.format(ndata, ntotal, 100 * ndata / ntotal,
                                                                     epoch_loss / ntracked)
                 if hyper_opt is not None:
-                    sig2, ell = (float(v.detach().cpu()) for v in mod.get_kernel_params())
+                    sig2, ell = (v.detach().cpu() for v in mod.get_kernel_params())
+                    sig2 = float(sig2)
+                    ell = float(ell) if ell.numel() == 1 else ell.numpy()
                     if learn_kernel:
                         sig2_list.append(np.array(sig2))
                         ell_list.append(np.array(ell))
-                        msg += ' sig2={:.4f} ell={:.4f}'.format(sig2, ell)
+                        ell_txt = '{:.4f}'.format(ell) if np.ndim(ell) == 0 else \
+                            '(' + ', '.join('{:.4f}'.format(e) for e in ell) + ')'
+                        msg += ' sig2={:.4f} ell={}'.format(sig2, ell_txt)
                     if learn_noise:
                         noisesq = float(torch.exp(mod.log_noise2).detach().cpu())
                         noisesq_list.append(np.array(noisesq))

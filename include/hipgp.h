@@ -465,6 +465,62 @@ int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, co
  * HGP_E_ARG: ndim outside 1..3, a null pointer, a grid size < 1. */
 int hgp_kuf_win_bins(int ndim, const int64_t* m, int64_t* tile_out, int64_t* nbins_out);
 
+/* ---- SqExp with one length scale per axis ("ARD"), point observations -------------------------
+ * The reference's SqExp takes ell as "a scalar, or a tensor that matches the dimension of data"
+ * (kernels.py:73-79):  k(x, u) = sig2 exp(-sum_a ((x_a - u_a) / ell[a])^2 / 2).  The six entries
+ * below are the point-observation entries above with `const double* ell` (ndim host values, read
+ * during the call) in place of `double ell`, and for the windowed pair `const double* rho` (ndim
+ * host values) in place of `double rho`.  Everything else (layouts, summation orders, scratch,
+ * nsplit, determinism, the remaining errors) is the scalar entry's; the scalar entries run the same
+ * launch code with their one value on every axis, so equal ell[a] (and rho[a]) give the scalar
+ * entry's bits.  Rules of all six, checked before any HIP call: kind must be HGP_KERN_SQEXP (the
+ * reference's Matern formula, kernels.py:145-158, defines no vector ell), every ell[a] finite and
+ * > 0, every rho[a] finite and >= 0, ell / rho non-null; else HGP_E_ARG. */
+
+/* hgp_kuf_grid with ell[a] per axis (kernels.py:73-79 with a vector ell). */
+int hgp_kuf_grid_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                     const void* x, int64_t nobs, double sig2, const double* ell, void* out,
+                     void* hip_stream);
+
+/* hgp_kuf_grid_matvec with ell[a] per axis (kernels.py:73-79). */
+int hgp_kuf_grid_matvec_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                            const void* x, int64_t nobs, double sig2, const double* ell,
+                            const void* w, int64_t nw, int64_t nsplit, void* out, void* hip_stream);
+
+/* hgp_kuf_grid_rmatvec with ell[a] per axis (kernels.py:73-79). */
+int hgp_kuf_grid_rmatvec_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                             const void* x, int64_t nobs, double sig2, const double* ell,
+                             const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream);
+
+/* hgp_kuf_grid_matvec_win with ell[a] and a radius rho[a] per axis (kernels.py:73-79).  Pair (n, j)
+ * is in the window iff fabs(x[n][a] - g_a[j_a]) <= rho[a] on every axis a, in dtype, each rho[a]
+ * rounded once to dtype.  With rho[a] the distance from which axis a's factor
+ * exp(-(r / ell[a])^2 / 2) is <= tol, a dropped pair has an axis whose factor is <= tol while the
+ * others are <= 1, so the scalar entry's bound holds: |dense - windowed| <= tol sig2 sum_j |w[s, j]|. */
+int hgp_kuf_grid_matvec_win_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                                const void* x, int64_t nobs, double sig2, const double* ell,
+                                const double* rho, const void* w, int64_t nw, void* out,
+                                void* hip_stream);
+
+/* hgp_kuf_grid_rmatvec_win over that window (kernels.py:73-79): the same predicate and the same
+ * element values as hgp_kuf_grid_matvec_win_ard, so the two are exact transposes.  order / bin_start
+ * as the scalar entry reads them (hgp_kuf_win_bins: the bins do not depend on the radius). */
+int hgp_kuf_grid_rmatvec_win_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                                 const void* x, int64_t nobs, double sig2, const double* ell,
+                                 const double* rho, const void* c, int64_t nc, const int64_t* order,
+                                 const int64_t* bin_start, void* out, void* hip_stream);
+
+/* Backward of hgp_kuf_grid_ard (the autograd of kernels.py:73-79 with a vector ell): with g (nobs, M)
+ * the upstream gradient, 1 + ndim sums of dtype on the device,
+ *   grad[0] = sum g dK/dsig2,   grad[1 + a] = sum g dK/dell[a],  dK/dell[a] = K ((x_a - u_a) / ell[a])^2 / ell[a].
+ * The tiles, the fp64 sums in a fixed order without atomics and the bit-reproducible result of
+ * hgp_kuf_grid_grad; grad[0] has that entry's bits when all ell[a] are equal, and the per-axis sums
+ * then add up to its dK/dell sum to rounding.  nobs = 0: 1 + ndim zeros.  Scratch: at most 2048
+ * times 4 fp64, stream-ordered. */
+int hgp_kuf_grid_grad_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
+                          const void* x, int64_t nobs, double sig2, const double* ell,
+                          const void* g, void* grad, void* hip_stream);
+
 /* hgp_kuf_semi_mc_matvec over the WINDOW of a line, for kernels far shorter than the grid (the
  * Monte-Carlo line integral of Kernel.k_semi_mc, kernels.py:19-39, summed over a tube around the
  * segment in place of the whole mesh):
