@@ -1,4 +1,5 @@
-// hgp_api.hip — plan object and the extern "C" ABI of libhipgp.so (see include/hipgp.h).
+// hgp_api.hip — plan object and the plan side of the extern "C" ABI of libhipgp.so (see include/hipgp.h); the
+// observation-side entries (hgp_kuf_*, hgp_rff_*, hgp_knn_doubly_diag) are in hgp_kuf_api.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -22,22 +23,20 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
+}  // namespace
+
+int hgp::fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+
+namespace {
 
 #define HIP_TRY(expr)                                                                              \
   do {                                                                                             \
     hipError_t _e = (expr);                                                                        \
     if (_e != hipSuccess)                                                                          \
       return fail(HGP_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                   \
-  } while (0)
-
-#define HGP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    int _rc = (expr);                                                                              \
-    if (_rc != 0) return _rc;                                                                      \
   } while (0)
 
 // smallest 3 * 2^k >= v with k >= 3 (a transform half-length 3 * 2^(k-1) >= 12, hgp_fft.hpp is_tri)
@@ -2494,486 +2493,6 @@ int hgp_rowdot(int dtype, const void* a, const void* c, void* out, int64_t nrhs,
   HIP_TRY(hipEventRecord(sc->ev, s));
   sc->last = s;
   sc->used = true;
-  return 0;
-}
-
-// ---- one length scale (and one window radius) per axis: the point-observation launchers take three values ----
-// a scalar entry's ell or rho on every axis
-struct KufRep3 {
-  double v[3];
-  explicit KufRep3(double a) : v{a, a, a} {}
-};
-
-// What the _ard entries check ahead of the scalar entries' own checks, all before any HIP call: the kernel,
-// ndim (ell and rho hold ndim values), every ell[a] finite and > 0, every rho[a] finite and >= 0 (rho == nullptr
-// with want_rho == false: the entry has none).  e3 / r3: the values, the last one repeated on the absent axes.
-static int check_ard_args(int kind, int ndim, const double* ell, const double* rho, bool want_rho, double* e3,
-                          double* r3) {
-  if (kind != HGP_KERN_SQEXP) return fail(HGP_E_ARG, "a length scale per axis is defined for HGP_KERN_SQEXP only");
-  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
-  if (ell == nullptr || (want_rho && rho == nullptr)) return fail(HGP_E_ARG, "null ell / rho");
-  for (int a = 0; a < ndim; ++a) {
-    if (!(ell[a] > 0) || !std::isfinite(ell[a])) return fail(HGP_E_ARG, "every ell[a] must be finite and > 0");
-    if (want_rho && (!(rho[a] >= 0) || !std::isfinite(rho[a])))
-      return fail(HGP_E_ARG, "every rho[a] must be finite and >= 0");
-  }
-  for (int a = 0; a < 3; ++a) {
-    e3[a] = ell[a < ndim ? a : ndim - 1];
-    if (want_rho) r3[a] = rho[a < ndim ? a : ndim - 1];
-  }
-  return 0;
-}
-
-static int kuf_grid_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
-                          const void* x, int64_t nobs, double sig2, const double* ell3, void* out,
-                          void* hip_stream) {
-  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (nobs == 0) return 0;
-  if (nobs < 0 || x == nullptr || out == nullptr) return fail(HGP_E_ARG, "bad x/out/nobs");
-  for (int a = 0; a < ndim; ++a)
-    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-  hipError_t e = kuf_grid(dtype, kind, ndim, m, grids, x, nobs, sig2, ell3, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                 int64_t nobs, double sig2, double ell, void* out, void* hip_stream) {
-  return kuf_grid_entry("hgp_kuf_grid", dtype, kind, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, out, hip_stream);
-}
-
-int hgp_kuf_grid_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                     int64_t nobs, double sig2, const double* ell, void* out, void* hip_stream) {
-  double e3[3];
-  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
-  return kuf_grid_entry("hgp_kuf_grid_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, out, hip_stream);
-}
-
-static int check_grid_args(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                           int64_t nobs, const void* out) {
-  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (nobs < 0 || (nobs > 0 && (x == nullptr || out == nullptr))) return fail(HGP_E_ARG, "bad x/out/nobs");
-  for (int a = 0; a < ndim; ++a)
-    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-  return 0;
-}
-
-int hgp_kuf_semi_mc(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
-                    const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, void* out,
-                    void* hip_stream) {
-  HGP_TRY(check_grid_args(dtype, ndim, m, grids, x, nobs, out));
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_GNEITING) return fail(HGP_E_ARG, "bad kernel kind");
-  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
-  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
-  if (nobs == 0) return 0;
-  hipError_t e = kuf_semi(dtype, kind, kparam, ndim, m, grids, x, nobs, sig2, ell, npts, u, out,
-                          reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_sqexp(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
-                       double sig2, double ell, void* out, void* hip_stream) {
-  HGP_TRY(check_grid_args(dtype, ndim, m, grids, x, nobs, out));
-  if (nobs == 0) return 0;
-  hipError_t e = kuf_semi(dtype, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, out,
-                          reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// the checks the three (sig2, ell) backward entries share; all before any HIP call
-static int check_grad_args(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                           int64_t nobs, const void* g, const void* grad2) {
-  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_GNEITING) return fail(HGP_E_ARG, "bad kernel kind");
-  if (grad2 == nullptr) return fail(HGP_E_ARG, "grad2 is null");
-  if (nobs < 0 || (nobs > 0 && (x == nullptr || g == nullptr))) return fail(HGP_E_ARG, "bad x/g/nobs");
-  for (int a = 0; a < ndim; ++a)
-    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-  if (kind == HGP_KERN_GNEITING)
-    return fail(HGP_E_UNSUPPORTED, "no hyper-parameter gradient for the Gneiting kernel (the reference's is NaN at r = 0)");
-  return 0;
-}
-
-int hgp_kuf_grid_grad(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                      int64_t nobs, double sig2, double ell, const void* g, void* grad2, void* hip_stream) {
-  HGP_TRY(check_grad_args(dtype, kind, ndim, m, grids, x, nobs, g, grad2));
-  hipError_t e = kuf_grad(dtype, 0, kind, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, g, grad2,
-                          reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_grad: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_grid_grad_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                          int64_t nobs, double sig2, const double* ell, const void* g, void* grad, void* hip_stream) {
-  double e3[3];
-  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
-  HGP_TRY(check_grad_args(dtype, kind, ndim, m, grids, x, nobs, g, grad));
-  hipError_t e = kuf_grad_ard(dtype, ndim, m, grids, x, nobs, sig2, e3, g, grad, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_grid_grad_ard: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_mc_grad(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
-                         const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u,
-                         const void* g, void* grad2, void* hip_stream) {
-  (void)kparam;   // Gneiting's alpha: that kernel is refused below
-  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
-  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
-  HGP_TRY(check_grad_args(dtype, kind, ndim, m, grids, x, nobs, g, grad2));
-  hipError_t e = kuf_grad(dtype, 1, kind, ndim, m, grids, x, nobs, sig2, ell, npts, u, g, grad2,
-                          reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_grad: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_sqexp_grad(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                            int64_t nobs, double sig2, double ell, const void* g, void* grad2, void* hip_stream) {
-  HGP_TRY(check_grad_args(dtype, HGP_KERN_SQEXP, ndim, m, grids, x, nobs, g, grad2));
-  hipError_t e = kuf_grad(dtype, 2, HGP_KERN_SQEXP, ndim, m, grids, x, nobs, sig2, ell, 0, nullptr, g, grad2,
-                          reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_grad: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// the checks the three Kuf products share; all before any HIP call.  Returns 1 when there is
-// nothing to do (nobs = 0 or nw = 0), 0 to go on, else the error.
-static int check_matvec_args(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                             int64_t nobs, const void* w, int64_t nw, int64_t nsplit, const void* out) {
-  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (nobs < 0 || nw < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nw and nsplit must be >= 0");
-  for (int a = 0; a < ndim; ++a)
-    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-  if (nobs == 0 || nw == 0) return 1;
-  if (x == nullptr || w == nullptr || out == nullptr) return fail(HGP_E_ARG, "null x / w / out");
-  return 0;
-}
-
-static int kuf_grid_matvec_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
-                                 const void* const* grids, const void* x, int64_t nobs, double sig2,
-                                 const double* ell3, const void* w, int64_t nw, int64_t nsplit, void* out,
-                                 void* hip_stream) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, nsplit, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell3, 0, nullptr, w, nw, nsplit, out,
-                            reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_grid_matvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                        int64_t nobs, double sig2, double ell, const void* w, int64_t nw, int64_t nsplit, void* out,
-                        void* hip_stream) {
-  return kuf_grid_matvec_entry("hgp_kuf_grid_matvec", dtype, kind, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, w, nw,
-                               nsplit, out, hip_stream);
-}
-
-int hgp_kuf_grid_matvec_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                            int64_t nobs, double sig2, const double* ell, const void* w, int64_t nw, int64_t nsplit,
-                            void* out, void* hip_stream) {
-  double e3[3];
-  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
-  return kuf_grid_matvec_entry("hgp_kuf_grid_matvec_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, w, nw, nsplit,
-                               out, hip_stream);
-}
-
-int hgp_kuf_semi_mc_matvec(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
-                           const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u,
-                           const void* w, int64_t nw, int64_t nsplit, void* out, void* hip_stream) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_GNEITING) return fail(HGP_E_ARG, "bad kernel kind");
-  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
-  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, nsplit, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, npts, u, w, nw, nsplit, out,
-                            reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_matvec: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_sqexp_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                              int64_t nobs, double sig2, double ell, const void* w, int64_t nw, int64_t nsplit,
-                              void* out, void* hip_stream) {
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, nsplit, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, 0, nullptr, w, nw,
-                            nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_matvec: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// the checks the three transposed Kuf products share; all before any HIP call.  Returns 1 when
-// there is nothing to do (nc = 0), 0 to go on (nobs = 0 included: out is zeroed), else the error.
-static int check_rmatvec_args(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                              int64_t nobs, const void* c, int64_t nc, int64_t nsplit, const void* out) {
-  if (ndim < 1 || ndim > 3 || m == nullptr || grids == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m/grids non-null");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (nobs < 0 || nc < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nc and nsplit must be >= 0");
-  for (int a = 0; a < ndim; ++a)
-    if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-  if (nc == 0) return 1;
-  if (out == nullptr || (nobs > 0 && (x == nullptr || c == nullptr))) return fail(HGP_E_ARG, "null x / c / out");
-  return 0;
-}
-
-static int kuf_grid_rmatvec_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
-                                  const void* const* grids, const void* x, int64_t nobs, double sig2,
-                                  const double* ell3, const void* c, int64_t nc, int64_t nsplit, void* out,
-                                  void* hip_stream) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_rmatvec(dtype, 0, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell3, 0, nullptr, c, nc, nsplit, out,
-                             reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_grid_rmatvec(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                         int64_t nobs, double sig2, double ell, const void* c, int64_t nc, int64_t nsplit, void* out,
-                         void* hip_stream) {
-  return kuf_grid_rmatvec_entry("hgp_kuf_grid_rmatvec", dtype, kind, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, c,
-                                nc, nsplit, out, hip_stream);
-}
-
-int hgp_kuf_grid_rmatvec_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                             int64_t nobs, double sig2, const double* ell, const void* c, int64_t nc, int64_t nsplit,
-                             void* out, void* hip_stream) {
-  double e3[3];
-  HGP_TRY(check_ard_args(kind, ndim, ell, nullptr, false, e3, nullptr));
-  return kuf_grid_rmatvec_entry("hgp_kuf_grid_rmatvec_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, c, nc,
-                                nsplit, out, hip_stream);
-}
-
-int hgp_kuf_semi_mc_rmatvec(int dtype, int kind, double kparam, int ndim, const int64_t* m, const void* const* grids,
-                            const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u,
-                            const void* c, int64_t nc, int64_t nsplit, void* out, void* hip_stream) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_GNEITING) return fail(HGP_E_ARG, "bad kernel kind");
-  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
-  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_rmatvec(dtype, 1, kind, kparam, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, npts, u, c, nc, nsplit, out,
-                             reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_rmatvec: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_sqexp_rmatvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                               int64_t nobs, double sig2, double ell, const void* c, int64_t nc, int64_t nsplit,
-                               void* out, void* hip_stream) {
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, nsplit, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_rmatvec(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, KufRep3(ell).v, 0, nullptr, c, nc,
-                             nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_rmatvec: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// the windowed products: the dense entries' checks, and rho; all before any HIP call
-static int check_win_rho(double rho) {
-  if (!(rho >= 0) || !std::isfinite(rho)) return fail(HGP_E_ARG, "rho must be finite and >= 0");
-  return 0;
-}
-
-// the two windowed point products after the checks of the kernel and of rho, which differ between the scalar and the
-// _ard entries
-static int kuf_grid_matvec_win_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
-                                     const void* const* grids, const void* x, int64_t nobs, double sig2,
-                                     const double* ell3, const double* rho3, const void* w, int64_t nw, void* out,
-                                     void* hip_stream) {
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_matvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell3, rho3, w, nw, out,
-                                reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return 0;
-}
-
-static int kuf_grid_rmatvec_win_entry(const char* name, int dtype, int kind, int ndim, const int64_t* m,
-                                      const void* const* grids, const void* x, int64_t nobs, double sig2,
-                                      const double* ell3, const double* rho3, const void* c, int64_t nc,
-                                      const int64_t* order, const int64_t* bin_start, void* out, void* hip_stream) {
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  if (nobs > 0 && (order == nullptr || bin_start == nullptr)) return fail(HGP_E_ARG, "null order / bin_start");
-  hipError_t e = kuf_rmatvec_win(dtype, kind, ndim, m, grids, x, nobs, sig2, ell3, rho3, c, nc, order, bin_start, out,
-                                 reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string(name) + ": " + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_grid_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                            int64_t nobs, double sig2, double ell, double rho, const void* w, int64_t nw, void* out,
-                            void* hip_stream) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
-  HGP_TRY(check_win_rho(rho));
-  return kuf_grid_matvec_win_entry("hgp_kuf_grid_matvec_win", dtype, kind, ndim, m, grids, x, nobs, sig2,
-                                   KufRep3(ell).v, KufRep3(rho).v, w, nw, out, hip_stream);
-}
-
-int hgp_kuf_grid_matvec_win_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
-                                const void* x, int64_t nobs, double sig2, const double* ell, const double* rho,
-                                const void* w, int64_t nw, void* out, void* hip_stream) {
-  double e3[3], r3[3];
-  HGP_TRY(check_ard_args(kind, ndim, ell, rho, true, e3, r3));
-  return kuf_grid_matvec_win_entry("hgp_kuf_grid_matvec_win_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, r3, w,
-                                   nw, out, hip_stream);
-}
-
-int hgp_kuf_grid_rmatvec_win_ard(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
-                                 const void* x, int64_t nobs, double sig2, const double* ell, const double* rho,
-                                 const void* c, int64_t nc, const int64_t* order, const int64_t* bin_start, void* out,
-                                 void* hip_stream) {
-  double e3[3], r3[3];
-  HGP_TRY(check_ard_args(kind, ndim, ell, rho, true, e3, r3));
-  return kuf_grid_rmatvec_win_entry("hgp_kuf_grid_rmatvec_win_ard", dtype, kind, ndim, m, grids, x, nobs, sig2, e3, r3,
-                                    c, nc, order, bin_start, out, hip_stream);
-}
-
-int hgp_kuf_grid_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                             int64_t nobs, double sig2, double ell, double rho, const void* c, int64_t nc,
-                             const int64_t* order, const int64_t* bin_start, void* out, void* hip_stream) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // as hgp_kuf_grid
-  HGP_TRY(check_win_rho(rho));
-  return kuf_grid_rmatvec_win_entry("hgp_kuf_grid_rmatvec_win", dtype, kind, ndim, m, grids, x, nobs, sig2,
-                                    KufRep3(ell).v, KufRep3(rho).v, c, nc, order, bin_start, out, hip_stream);
-}
-
-// the windowed line-integral products: the dense entries' checks, rho, the kernel and the piece counts
-static int check_line_win(int kind, double rho, const int* pieces, int64_t npieces, int64_t nobs) {
-  if (kind < HGP_KERN_SQEXP || kind > HGP_KERN_MATERN52) return fail(HGP_E_ARG, "bad kernel kind");   // no Gneiting
-  HGP_TRY(check_win_rho(rho));
-  if (npieces != nobs) return fail(HGP_E_ARG, "pieces must hold nobs entries");
-  if (nobs > 0 && pieces == nullptr) return fail(HGP_E_ARG, "null pieces");
-  return 0;
-}
-
-int hgp_kuf_semi_mc_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
-                               const void* x, int64_t nobs, double sig2, double ell, double rho, int npts,
-                               const void* u, const int* pieces, int64_t npieces, const void* w, int64_t nw,
-                               void* out, void* hip_stream) {
-  HGP_TRY(check_line_win(kind, rho, pieces, npieces, nobs));
-  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
-  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_line_matvec_win(dtype, 1, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, w,
-                                     nw, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_matvec_win: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_sqexp_matvec_win(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                                  int64_t nobs, double sig2, double ell, double rho, const int* pieces,
-                                  int64_t npieces, const void* w, int64_t nw, void* out, void* hip_stream) {
-  HGP_TRY(check_line_win(HGP_KERN_SQEXP, rho, pieces, npieces, nobs));
-  const int c = check_matvec_args(dtype, ndim, m, grids, x, nobs, w, nw, 0, out);
-  if (c != 0) return c > 0 ? 0 : c;
-  hipError_t e = kuf_line_matvec_win(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, 0, nullptr,
-                                     pieces, w, nw, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_matvec_win: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_mc_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids,
-                                const void* x, int64_t nobs, double sig2, double ell, double rho, int npts,
-                                const void* u, const int* pieces, int64_t npieces, const void* c, int64_t nc,
-                                void* out, void* hip_stream) {
-  HGP_TRY(check_line_win(kind, rho, pieces, npieces, nobs));
-  if (npts < 1 || npts > 1024) return fail(HGP_E_ARG, "npts must be in [1, 1024]");
-  if (u == nullptr) return fail(HGP_E_ARG, "u (the device offset draw) is null");
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_line_rmatvec_win(dtype, 1, kind, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, c,
-                                      nc, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_mc_rmatvec_win: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_semi_sqexp_rmatvec_win(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                                   int64_t nobs, double sig2, double ell, double rho, const int* pieces,
-                                   int64_t npieces, const void* c, int64_t nc, void* out, void* hip_stream) {
-  HGP_TRY(check_line_win(HGP_KERN_SQEXP, rho, pieces, npieces, nobs));
-  const int r = check_rmatvec_args(dtype, ndim, m, grids, x, nobs, c, nc, 0, out);
-  if (r != 0) return r > 0 ? 0 : r;
-  hipError_t e = kuf_line_rmatvec_win(dtype, 2, HGP_KERN_SQEXP, 1.0, ndim, m, grids, x, nobs, sig2, ell, rho, 0,
-                                      nullptr, pieces, c, nc, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_kuf_semi_sqexp_rmatvec_win: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_kuf_win_bins(int ndim, const int64_t* m, int64_t* tile_out, int64_t* nbins_out) {
-  if (ndim < 1 || ndim > 3 || m == nullptr) return fail(HGP_E_ARG, "ndim must be 1..3, m non-null");
-  if (tile_out == nullptr || nbins_out == nullptr) return fail(HGP_E_ARG, "null tile_out / nbins_out");
-  for (int a = 0; a < ndim; ++a)
-    if (m[a] < 1) return fail(HGP_E_ARG, "grid sizes must be >= 1");
-  kuf_win_geometry(ndim, m, tile_out, nbins_out);
-  return 0;
-}
-
-int hgp_rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
-                   const void* omega, const void* phase, int64_t nfeat, const void* w, int64_t nw, double scale,
-                   int transposed, double beta, int64_t nsplit, void* out, void* hip_stream) {
-  // all checks before any HIP call
-  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if ((x == nullptr) == (grids == nullptr))
-    return fail(HGP_E_ARG, "the points are either x (explicit rows) or grids (the mesh): give exactly one");
-  if (nobs < 0 || nfeat < 0 || nw < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nfeat, nw and nsplit must be >= 0");
-  int64_t npoints = nobs;
-  if (x == nullptr) {
-    if (m == nullptr) return fail(HGP_E_ARG, "mesh mode needs m");
-    npoints = 1;
-    for (int a = 0; a < ndim; ++a) {
-      if (m[a] < 1 || grids[a] == nullptr) return fail(HGP_E_ARG, "grid sizes must be >= 1 with non-null grids");
-      npoints *= m[a];
-    }
-  }
-  if (npoints == 0 || nw == 0) return 0;
-  if (nfeat < 1) return fail(HGP_E_ARG, "nfeat must be >= 1 when there are points");
-  if (omega == nullptr || phase == nullptr || w == nullptr || out == nullptr)
-    return fail(HGP_E_ARG, "null omega / phase / w / out");
-  hipError_t e = rff_matvec(dtype, ndim, m, grids, x, npoints, omega, phase, nfeat, w, nw, scale, transposed != 0, beta,
-                            nsplit, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rff_matvec: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_rff_line_matvec(int dtype, int ndim, const void* x, int64_t nobs, const void* omega, const void* phase,
-                        int64_t nfeat, const void* w, int64_t nw, double scale, int transposed, double beta,
-                        int64_t nsplit, void* out, void* hip_stream) {
-  // all checks before any HIP call
-  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (x == nullptr) return fail(HGP_E_ARG, "null x: the lines are explicit rows (no mesh mode)");
-  if (nobs < 0 || nfeat < 0 || nw < 0 || nsplit < 0) return fail(HGP_E_ARG, "nobs, nfeat, nw and nsplit must be >= 0");
-  if (nobs == 0 || nw == 0) return 0;
-  if (nfeat < 1) return fail(HGP_E_ARG, "nfeat must be >= 1 when there are lines");
-  if (omega == nullptr || phase == nullptr || w == nullptr || out == nullptr)
-    return fail(HGP_E_ARG, "null omega / phase / w / out");
-  hipError_t e = rff_line_matvec(dtype, ndim, x, nobs, omega, phase, nfeat, w, nw, scale, transposed != 0, beta, nsplit,
-                                 out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_rff_line_matvec: ") + hipGetErrorString(e));
-  return 0;
-}
-
-int hgp_knn_doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* table,
-                        int N, void* out, void* hip_stream) {
-  if (ndim < 1 || ndim > 3) return fail(HGP_E_ARG, "ndim must be 1..3");
-  if (dtype != HGP_F32 && dtype != HGP_F64) return fail(HGP_E_ARG, "dtype must be HGP_F32 or HGP_F64");
-  if (N < 2 || table == nullptr) return fail(HGP_E_ARG, "table needs N >= 2 entries");
-  if (nobs < 0 || (nobs > 0 && (x == nullptr || out == nullptr))) return fail(HGP_E_ARG, "bad x/out/nobs");
-  if (nobs == 0) return 0;
-  hipError_t e = doubly_diag(dtype, ndim, x, nobs, sig2, ell, table, N, out, reinterpret_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(HGP_E_HIP, std::string("hgp_knn_doubly_diag: ") + hipGetErrorString(e));
   return 0;
 }
 

@@ -3,9 +3,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
 #include "hgp_pass.hpp"
 
+// an ABI entry's early return on a non-zero status
+#define HGP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    int _rc = (expr);                                                                              \
+    if (_rc != 0) return _rc;                                                                      \
+  } while (0)
+
 namespace hgp {
+
+// records msg as the calling thread's hgp_last_error() and returns code (hgp_api.hip: the one definition and string)
+int fail(int code, const std::string& msg);
 
 struct GridDims { int d; int64_t m[3]; int64_t n[3]; int64_t L[3]; };
 
@@ -87,52 +99,51 @@ template <typename T> void extract_cplx(const double2* F, void* o, int64_t n, in
                                         hipStream_t s, int64_t L0t = 0, int64_t L1t = 0);
 template <typename T> void expand_spec(const double* src, void* out, const GridDims& g, hipStream_t s);
 
-// dense grid cross covariance (hgp_kuf.hip)
-// ell of the point-observation launchers (kuf_grid, kuf_matvec, kuf_rmatvec, the _win pair): three host values,
-// one per axis; SqExp divides axis a by ell[a], Matern and the line integrals read ell[0].  rho likewise.
-hipError_t kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                    int64_t nobs, double sig2, const double* ell, void* out, hipStream_t s);
-hipError_t kuf_semi(int dtype, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                    const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, void* out,
-                    hipStream_t s);
+// ---- the observation-side ("Kuf") family: one record from the C entries (hgp_kuf_api.hip) to the launchers ----
+// One Kuf problem on the host.  ell / rho: three host values, one per axis (a scalar entry's value in each; an
+// _ard entry's last value on the absent axes): SqExp divides axis a by ell[a], Matern and the line integrals
+// read ell[0]; the window reads rho[a] on axis a, a line's tube rho[0].
+struct KufObs {
+  int dtype = 0;                        // HGP_F32 / HGP_F64
+  int mode = 0;                         // 0 point observations, 1 semi-mc, 2 semi-sqexp
+  int kind = 0;                         // HGP_KERN_*
+  double kp = 1.0;                      // Gneiting's alpha
+  int ndim = 0;
+  const int64_t* m = nullptr;
+  const void* const* grids = nullptr;
+  const void* x = nullptr;              // (nobs, ndim) rows
+  int64_t nobs = 0;
+  double sig2 = 0, ell[3] = {0, 0, 0}, rho[3] = {0, 0, 0};
+  int npts = 0;                         // mode 1: the Monte-Carlo points and the device offset draw
+  const void* u = nullptr;
+  const int* pieces = nullptr;          // the windowed line integrals: nobs device ints
+  hipStream_t stream = nullptr;
+};
+// dense cross covariances (hgp_kuf.hip): kuf_grid mode 0, kuf_semi modes 1 / 2
+hipError_t kuf_grid(const KufObs& o, void* out);
+hipError_t kuf_semi(const KufObs& o, void* out);
 hipError_t doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* tab,
                        int N, void* out, hipStream_t s);
-// (sig2, ell) backward of the three above; mode: 0 point observations, 1 semi-mc, 2 semi-sqexp
-hipError_t kuf_grad(int dtype, int mode, int kind, int ndim, const int64_t* m, const void* const* grids,
-                    const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* gup,
-                    void* grad2, hipStream_t s);
+// (sig2, ell) backward of the two above: grad2 = (sum g dK/dsig2, sum g dK/dell); nobs = 0: zeros
+hipError_t kuf_grad(const KufObs& o, const void* gup, void* grad2);
 // SqExp point observations with one ell per axis: grad = (sum g dK/dsig2, sum g dK/dell_a for a < ndim)
-hipError_t kuf_grad_ard(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
-                        double sig2, const double* ell, const void* gup, void* grad, hipStream_t s);
-// out = Kuf w^T without Kuf (hgp_kuf_mv.hip); mode as kuf_grad; nobs > 0, nw > 0, nsplit >= 0 (0: chosen here)
-hipError_t kuf_matvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                      const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
-                      const void* w, int64_t nw, int64_t nsplit, void* out, hipStream_t s);
-// out = c Kuf, the transposed product, without Kuf (hgp_kuf_rmv.hip); mode as kuf_grad; nobs >= 0 (0: out zeroed),
-// nc > 0, nsplit >= 0 (0: chosen here)
-hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                       const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
-                       const void* c, int64_t nc, int64_t nsplit, void* out, hipStream_t s);
-// the two point-observation products over the window |x_a - u_a| <= rho[a] per axis (hgp_kuf_win.hip); matvec: nobs > 0,
-// nw > 0; rmatvec: nobs >= 0 (0: out zeroed), nc > 0, order / bin_start as kuf_win_geometry lays the bins out
-hipError_t kuf_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                          int64_t nobs, double sig2, const double* ell, const double* rho, const void* w, int64_t nw,
-                          void* out, hipStream_t s);
-hipError_t kuf_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                           int64_t nobs, double sig2, const double* ell, const double* rho, const void* c, int64_t nc,
-                           const int64_t* order, const int64_t* bin_start, void* out, hipStream_t s);
+hipError_t kuf_grad_ard(const KufObs& o, const void* gup, void* grad);
+// out = Kuf w^T without Kuf (hgp_kuf_mv.hip); nobs > 0, nw > 0, nsplit >= 0 (0: chosen here)
+hipError_t kuf_matvec(const KufObs& o, const void* w, int64_t nw, int64_t nsplit, void* out);
+// out = c Kuf, the transposed product, without Kuf (hgp_kuf_rmv.hip); nobs >= 0 (0: out zeroed), nc > 0,
+// nsplit >= 0 (0: chosen here)
+hipError_t kuf_rmatvec(const KufObs& o, const void* c, int64_t nc, int64_t nsplit, void* out);
+// the two point-observation products over the window |x_a - u_a| <= rho[a] per axis (hgp_kuf_win.hip); matvec:
+// nobs > 0, nw > 0; rmatvec: nobs >= 0 (0: out zeroed), nc > 0, order / bin_start as kuf_win_geometry lays the
+// bins out
+hipError_t kuf_matvec_win(const KufObs& o, const void* w, int64_t nw, void* out);
+hipError_t kuf_rmatvec_win(const KufObs& o, const void* c, int64_t nc, const int64_t* order,
+                           const int64_t* bin_start, void* out);
 void kuf_win_geometry(int ndim, const int64_t* m, int64_t* tile, int64_t* nbins);
-// the two line-integral products over the window of a line: the nodes within rho of a piece of its segment
-// (hgp_kuf_line_win.hip); mode 1 semi-mc, 2 semi-sqexp; pieces: nobs device ints; matvec: nobs > 0, nw > 0;
-// rmatvec: nobs >= 0 (0: out zeroed), nc > 0
-hipError_t kuf_line_matvec_win(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m,
-                               const void* const* grids, const void* x, int64_t nobs, double sig2, double ell,
-                               double rho, int npts, const void* u, const int* pieces, const void* w, int64_t nw,
-                               void* out, hipStream_t s);
-hipError_t kuf_line_rmatvec_win(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m,
-                                const void* const* grids, const void* x, int64_t nobs, double sig2, double ell,
-                                double rho, int npts, const void* u, const int* pieces, const void* c, int64_t nc,
-                                void* out, hipStream_t s);
+// the two line-integral products (mode 1 / 2) over the window of a line: the nodes within rho[0] of a piece of
+// its segment (hgp_kuf_line_win.hip); matvec: nobs > 0, nw > 0; rmatvec: nobs >= 0 (0: out zeroed), nc > 0
+hipError_t kuf_line_matvec_win(const KufObs& o, const void* w, int64_t nw, void* out);
+hipError_t kuf_line_rmatvec_win(const KufObs& o, const void* c, int64_t nc, void* out);
 // out = beta out + scale w cos(2 pi (omega . p + phase)) without the features (hgp_rff.hip); x == nullptr: the points
 // are the mesh of (m, grids), else npoints rows of x; npoints > 0, nfeat > 0, nw > 0, nsplit >= 0 (0: chosen here)
 hipError_t rff_matvec(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t npoints,

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "hgp_kuf_eval.hpp"   // KufGrid, scaled_dist, kern_eval: shared with every product kernel
+#include "hgp_kuf_launch.hpp" // KufObs, the grid descriptor and the dtype ladder
 #include "hgp_kuf_semi.hpp"   // the line-integral element: its one definition
 
 namespace hgp {
@@ -174,41 +175,30 @@ __global__ __launch_bounds__(256) void k_doubly_diag(const T* __restrict__ x, in
   out[n] = ell * ell * sig2 * iv;
 }
 
-hipError_t kuf_semi(int dtype, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                    const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, void* out,
-                    hipStream_t s) {
+// g from the record; the forwards' tiles: (observation, outer index, chunk of the last axis)
+static int64_t kuf_fwd_tiles(const KufObs& o, KufGrid& g) {
+  int64_t outer;
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, nullptr, &outer);
+  return o.nobs * outer * ((o.m[o.ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK);
+}
+
+// launcher behind hgp_kuf_semi_mc (mode 1) / hgp_kuf_semi_sqexp (mode 2)
+hipError_t kuf_semi(const KufObs& o, void* out) {
   KufGrid g{};
-  g.d = ndim;
-  int64_t outer = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    if (a < ndim - 1) outer *= m[a];
-  }
-  const int64_t nchunk = (m[ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK;
-  const int64_t nb = nobs * outer * nchunk;
+  const int64_t nb = kuf_fwd_tiles(o, g);
   if (nb > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  const bool mc = npts > 0;
-  if (dtype == HGP_F32) {
-    const float* xf = reinterpret_cast<const float*>(x);
-    float* of = reinterpret_cast<float*>(out);
-    if (mc)
-      hipLaunchKernelGGL((k_kuf_semi_mc<float>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g, xf, nobs, kind,
-                         (float)sig2, (float)ell, (float)kp, npts, reinterpret_cast<const float*>(u), of);
+  return kuf_with_dtype(o.dtype, [&](auto t) {
+    using T = decltype(t);
+    const T* x = reinterpret_cast<const T*>(o.x);
+    if (o.mode == 1)
+      hipLaunchKernelGGL((k_kuf_semi_mc<T>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, o.stream, g, x, o.nobs, o.kind,
+                         (T)o.sig2, (T)o.ell[0], (T)o.kp, o.npts, reinterpret_cast<const T*>(o.u),
+                         reinterpret_cast<T*>(out));
     else
-      hipLaunchKernelGGL((k_kuf_semi_sqexp<float>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g, xf, nobs,
-                         (float)sig2, (float)ell, of);
-  } else {
-    const double* xd = reinterpret_cast<const double*>(x);
-    double* od = reinterpret_cast<double*>(out);
-    if (mc)
-      hipLaunchKernelGGL((k_kuf_semi_mc<double>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g, xd, nobs, kind,
-                         sig2, ell, kp, npts, reinterpret_cast<const double*>(u), od);
-    else
-      hipLaunchKernelGGL((k_kuf_semi_sqexp<double>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g, xd, nobs, sig2,
-                         ell, od);
-  }
-  return hipGetLastError();
+      hipLaunchKernelGGL((k_kuf_semi_sqexp<T>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, o.stream, g, x, o.nobs,
+                         (T)o.sig2, (T)o.ell[0], reinterpret_cast<T*>(out));
+    return hipGetLastError();
+  });
 }
 
 hipError_t doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double sig2, double ell, const void* tab,
@@ -224,30 +214,18 @@ hipError_t doubly_diag(int dtype, int ndim, const void* x, int64_t nobs, double 
   return hipGetLastError();
 }
 
-// launcher behind hgp_kuf_grid / hgp_kuf_grid_ard (argument checks in hgp_api.hip); ell: one value per
-// axis, three in all (the scalar entry's value in each)
-hipError_t kuf_grid(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                    int64_t nobs, double sig2, const double* ell, void* out, hipStream_t s) {
+// launcher behind hgp_kuf_grid / hgp_kuf_grid_ard (argument checks in hgp_kuf_api.hip)
+hipError_t kuf_grid(const KufObs& o, void* out) {
   KufGrid g{};
-  g.d = ndim;
-  int64_t outer = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    if (a < ndim - 1) outer *= m[a];
-  }
-  const int64_t nchunk = (m[ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK;
-  const int64_t nb = nobs * outer * nchunk;
+  const int64_t nb = kuf_fwd_tiles(o, g);
   if (nb > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  if (dtype == HGP_F32)
-    hipLaunchKernelGGL((k_kuf_grid<float>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g,
-                       reinterpret_cast<const float*>(x), nobs, kind, (float)sig2, kuf_vec<float>(ell),
-                       reinterpret_cast<float*>(out));
-  else
-    hipLaunchKernelGGL((k_kuf_grid<double>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, s, g,
-                       reinterpret_cast<const double*>(x), nobs, kind, sig2, kuf_vec<double>(ell),
-                       reinterpret_cast<double*>(out));
-  return hipGetLastError();
+  return kuf_with_dtype(o.dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_kuf_grid<T>), dim3((unsigned)nb), dim3(KUF_THREADS), 0, o.stream, g,
+                       reinterpret_cast<const T*>(o.x), o.nobs, o.kind, (T)o.sig2, kuf_vec<T>(o.ell),
+                       reinterpret_cast<T*>(out));
+    return hipGetLastError();
+  });
 }
 
 // ---- backward of the three cross covariances with respect to (sig2, ell) ---------------------
@@ -470,38 +448,42 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grad_finish_ard(const doubl
   if (threadIdx.x >= 1 && (int)threadIdx.x <= d) grad[threadIdx.x] = (T)(sig2 * tot[threadIdx.x]);
 }
 
-template <typename T>
-static hipError_t kuf_grad_ard_t(int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
-                                 double sig2, const double* ell, const void* gup, void* grad, hipStream_t s) {
-  if (nobs == 0) return hipMemsetAsync(grad, 0, (size_t)(1 + ndim) * sizeof(T), s);
+// nblk blocks over the forwards' ntile tiles leave one row of `sums` fp64 partials each; finish(part) adds them up
+template <typename L, typename F>
+static hipError_t kuf_grad_run(const KufObs& o, int sums, L&& launch, F&& finish) {
   KufGrid g{};
-  g.d = ndim;
-  int64_t outer = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    if (a < ndim - 1) outer *= m[a];
-  }
-  const int64_t nchunk = (m[ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK;
-  const int64_t ntile = nobs * outer * nchunk;
+  const int64_t ntile = kuf_fwd_tiles(o, g);
   const int nblk = (int)(ntile < KUF_GRAD_BLOCKS ? ntile : KUF_GRAD_BLOCKS);
   double* part = nullptr;
-  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)nblk * KUF_ARD_SUMS * sizeof(double), s);
+  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)nblk * sums * sizeof(double), o.stream);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_kuf_grid_grad_ard<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g,
-                     reinterpret_cast<const T*>(x), kuf_vec<T>(ell), reinterpret_cast<const T*>(gup), ntile, part);
-  hipLaunchKernelGGL((k_kuf_grad_finish_ard<T>), dim3(1), dim3(KUF_THREADS), 0, s, part, nblk, ndim, sig2,
-                     reinterpret_cast<T*>(grad));
+  launch(g, ntile, nblk, part);
+  finish(nblk, part);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  return hipFreeAsync(part, s);
+  return hipFreeAsync(part, o.stream);
+}
+
+template <typename T>
+static hipError_t kuf_grad_ard_t(const KufObs& o, const void* gup, void* grad) {
+  hipStream_t s = o.stream;
+  if (o.nobs == 0) return hipMemsetAsync(grad, 0, (size_t)(1 + o.ndim) * sizeof(T), s);
+  return kuf_grad_run(
+      o, KUF_ARD_SUMS,
+      [&](const KufGrid& g, int64_t ntile, int nblk, double* part) {
+        hipLaunchKernelGGL((k_kuf_grid_grad_ard<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g,
+                           reinterpret_cast<const T*>(o.x), kuf_vec<T>(o.ell), reinterpret_cast<const T*>(gup), ntile,
+                           part);
+      },
+      [&](int nblk, double* part) {
+        hipLaunchKernelGGL((k_kuf_grad_finish_ard<T>), dim3(1), dim3(KUF_THREADS), 0, s, part, nblk, o.ndim, o.sig2,
+                           reinterpret_cast<T*>(grad));
+      });
 }
 
 // launcher behind hgp_kuf_grid_grad_ard: SqExp, point observations, grad holds 1 + ndim values
-hipError_t kuf_grad_ard(int dtype, int ndim, const int64_t* m, const void* const* grids, const void* x, int64_t nobs,
-                        double sig2, const double* ell, const void* gup, void* grad, hipStream_t s) {
-  if (dtype == HGP_F32) return kuf_grad_ard_t<float>(ndim, m, grids, x, nobs, sig2, ell, gup, grad, s);
-  return kuf_grad_ard_t<double>(ndim, m, grids, x, nobs, sig2, ell, gup, grad, s);
+hipError_t kuf_grad_ard(const KufObs& o, const void* gup, void* grad) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_grad_ard_t<decltype(t)>(o, gup, grad); });
 }
 
 // k_semi_mc is |x_n| mean_a k(u_j, alpha_a x_n) and neither |x_n| nor alpha_a depends on the
@@ -667,51 +649,34 @@ __global__ __launch_bounds__(KUF_THREADS) void k_kuf_grad_finish(const double* _
   }
 }
 
-// mode: 0 point observations, 1 semi-mc, 2 semi-sqexp
 template <typename T>
-static hipError_t kuf_grad_t(int mode, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                             int64_t nobs, double sig2, double ell, int npts, const void* u, const void* gup,
-                             void* grad2, hipStream_t s) {
-  if (nobs == 0) return hipMemsetAsync(grad2, 0, 2 * sizeof(T), s);
-  KufGrid g{};
-  g.d = ndim;
-  int64_t outer = 1;
-  for (int a = 0; a < ndim; ++a) {
-    g.m[a] = m[a];
-    g.g[a] = grids[a];
-    if (a < ndim - 1) outer *= m[a];
-  }
-  const int64_t nchunk = (m[ndim - 1] + KUF_CHUNK - 1) / KUF_CHUNK;
-  const int64_t ntile = nobs * outer * nchunk;
-  const int nblk = (int)(ntile < KUF_GRAD_BLOCKS ? ntile : KUF_GRAD_BLOCKS);
-  double* part = nullptr;
-  hipError_t e = hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)nblk * 2 * sizeof(double), s);
-  if (e != hipSuccess) return e;
-  const T* xt = reinterpret_cast<const T*>(x);
-  const T* gt = reinterpret_cast<const T*>(gup);
-  if (mode == 0)
-    hipLaunchKernelGGL((k_kuf_grid_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, kind, (T)ell, gt,
-                       ntile, part);
-  else if (mode == 1)
-    hipLaunchKernelGGL((k_kuf_semi_mc_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, kind, (T)ell,
-                       npts, reinterpret_cast<const T*>(u), gt, ntile, part);
-  else
-    hipLaunchKernelGGL((k_kuf_semi_sqexp_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, (T)ell, gt,
-                       ntile, part);
-  hipLaunchKernelGGL((k_kuf_grad_finish<T>), dim3(1), dim3(KUF_THREADS), 0, s, part, nblk, sig2,
-                     reinterpret_cast<T*>(grad2));
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return hipFreeAsync(part, s);
+static hipError_t kuf_grad_t(const KufObs& o, const void* gup, void* grad2) {
+  hipStream_t s = o.stream;
+  if (o.nobs == 0) return hipMemsetAsync(grad2, 0, 2 * sizeof(T), s);
+  return kuf_grad_run(
+      o, 2,
+      [&](const KufGrid& g, int64_t ntile, int nblk, double* part) {
+        const T* xt = reinterpret_cast<const T*>(o.x);
+        const T* gt = reinterpret_cast<const T*>(gup);
+        if (o.mode == 0)
+          hipLaunchKernelGGL((k_kuf_grid_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, o.kind,
+                             (T)o.ell[0], gt, ntile, part);
+        else if (o.mode == 1)
+          hipLaunchKernelGGL((k_kuf_semi_mc_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt, o.kind,
+                             (T)o.ell[0], o.npts, reinterpret_cast<const T*>(o.u), gt, ntile, part);
+        else
+          hipLaunchKernelGGL((k_kuf_semi_sqexp_grad<T>), dim3((unsigned)nblk), dim3(KUF_THREADS), 0, s, g, xt,
+                             (T)o.ell[0], gt, ntile, part);
+      },
+      [&](int nblk, double* part) {
+        hipLaunchKernelGGL((k_kuf_grad_finish<T>), dim3(1), dim3(KUF_THREADS), 0, s, part, nblk, o.sig2,
+                           reinterpret_cast<T*>(grad2));
+      });
 }
 
 // launcher behind hgp_kuf_grid_grad / hgp_kuf_semi_mc_grad / hgp_kuf_semi_sqexp_grad
-hipError_t kuf_grad(int dtype, int mode, int kind, int ndim, const int64_t* m, const void* const* grids,
-                    const void* x, int64_t nobs, double sig2, double ell, int npts, const void* u, const void* gup,
-                    void* grad2, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_grad_t<float>(mode, kind, ndim, m, grids, x, nobs, sig2, ell, npts, u, gup, grad2, s);
-  return kuf_grad_t<double>(mode, kind, ndim, m, grids, x, nobs, sig2, ell, npts, u, gup, grad2, s);
+hipError_t kuf_grad(const KufObs& o, const void* gup, void* grad2) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_grad_t<decltype(t)>(o, gup, grad2); });
 }
 
 }  // namespace hgp

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "hgp_internal.hpp"   // KufObs
 #include "hgp_kuf_eval.hpp"
 
 namespace hgp {
@@ -61,6 +62,12 @@ inline void kuf_fill_grid(KufGrid& g, int ndim, const int64_t* m, const void* co
 
 template <int V>
 using KufConst = std::integral_constant<int, V>;
+
+// f(T{}) for the tensor dtype T: what is left of a launcher's dtype wrapper
+template <typename F>
+inline hipError_t kuf_with_dtype(int dtype, F&& f) {
+  return dtype == HGP_F32 ? f(float{}) : f(double{});
+}
 
 // f(KufConst<NW>{}) for the group width NW in {8, 4, 1}
 template <typename F>

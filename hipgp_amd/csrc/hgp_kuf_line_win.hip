@@ -380,18 +380,17 @@ __global__ __launch_bounds__(LW_THREADS) void k_kuf_line_win_rmv(KufGrid g, cons
     if (s < ncv) out[(int64_t)s * M + j] = (T)acc[s];
 }
 
-// mode 1: semi-mc, 2: semi-sqexp.  nobs > 0, nw > 0
+// nobs > 0, nw > 0
 template <typename T>
-static hipError_t kuf_line_matvec_win_t(int mode, int kind, double kp, int ndim, const int64_t* m,
-                                        const void* const* grids, const void* xv, int64_t nobs, double sig2,
-                                        double ell, double rho, int npts, const void* uv, const int* pieces,
-                                        const void* wv, int64_t nw, void* outv, hipStream_t s) {
+static hipError_t kuf_line_matvec_win_t(const KufObs& o, const void* wv, int64_t nw, void* outv) {
+  const int64_t nobs = o.nobs;
+  hipStream_t s = o.stream;
   KufGrid g{};
   int64_t M, outer;
-  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
-  const T* x = reinterpret_cast<const T*>(xv);
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, &M, &outer);
+  const T* x = reinterpret_cast<const T*>(o.x);
   const T* w = reinterpret_cast<const T*>(wv);
-  const T* u = reinterpret_cast<const T*>(uv);
+  const T* u = reinterpret_cast<const T*>(o.u);
   T* out = reinterpret_cast<T*>(outv);
   // the split: a pure function of (nobs, the grid) and the CU count; a slice is a share of the rows
   // of the line's own outer bounding range
@@ -406,11 +405,11 @@ static hipError_t kuf_line_matvec_win_t(int mode, int kind, double kp, int ndim,
   return kuf_row_groups(
       nw, nsplit > 1 ? (size_t)nsplit * (size_t)nobs : 0, s,
       [&](int64_t s0, int NW, int nwv, double* part) {
-        kuf_with_mode(mode, [&](auto MD) {
+        kuf_with_mode(o.mode, [&](auto MD) {
           kuf_with_width(NW, [&](auto W) {
             hipLaunchKernelGGL((k_kuf_line_win_mv<T, decltype(MD)::value, decltype(W)::value>), dim3(nb),
-                               dim3(LW_WAVE), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces,
-                               w + s0 * M, nwv, M, (int)nsplit, part, out + s0, nw);
+                               dim3(LW_WAVE), 0, s, g, x, nobs, o.kind, (T)o.sig2, (T)o.ell[0], (T)o.kp, (T)o.rho[0],
+                               o.npts, u, o.pieces, w + s0 * M, nwv, M, (int)nsplit, part, out + s0, nw);
           });
         });
       },
@@ -423,57 +422,41 @@ static hipError_t kuf_line_matvec_win_t(int mode, int kind, double kp, int ndim,
 
 // nobs >= 0 (0: out zeroed), nc > 0
 template <typename T>
-static hipError_t kuf_line_rmatvec_win_t(int mode, int kind, double kp, int ndim, const int64_t* m,
-                                         const void* const* grids, const void* xv, int64_t nobs, double sig2,
-                                         double ell, double rho, int npts, const void* uv, const int* pieces,
-                                         const void* cv, int64_t nc, void* outv, hipStream_t s) {
+static hipError_t kuf_line_rmatvec_win_t(const KufObs& o, const void* cv, int64_t nc, void* outv) {
+  const int64_t nobs = o.nobs;
+  hipStream_t s = o.stream;
   KufGrid g{};
-  int64_t M, outer;
-  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
+  int64_t M;
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, &M);
   T* out = reinterpret_cast<T*>(outv);
   if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
-  const T* x = reinterpret_cast<const T*>(xv);
+  const T* x = reinterpret_cast<const T*>(o.x);
   const T* c = reinterpret_cast<const T*>(cv);
-  const T* u = reinterpret_cast<const T*>(uv);
-  const int64_t ntile = kuf_tile_count(ndim, m);
+  const T* u = reinterpret_cast<const T*>(o.u);
+  const int64_t ntile = kuf_tile_count(o.ndim, o.m);
   if (ntile > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)ntile;
   return kuf_row_groups(nc, s, [&](int64_t s0, int NC, int ncv, double*) {
-    kuf_with_mode(mode, [&](auto MD) {
-      kuf_with_dim(ndim, [&](auto D) {
+    kuf_with_mode(o.mode, [&](auto MD) {
+      kuf_with_dim(o.ndim, [&](auto D) {
         kuf_with_width(NC, [&](auto W) {
           hipLaunchKernelGGL(
               (k_kuf_line_win_rmv<T, decltype(MD)::value, decltype(W)::value, decltype(D)::value>), dim3(nb),
-              dim3(LW_THREADS), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, (T)rho, npts, u, pieces,
-              c + s0 * nobs, ncv, M, out + s0 * M);
+              dim3(LW_THREADS), 0, s, g, x, nobs, o.kind, (T)o.sig2, (T)o.ell[0], (T)o.kp, (T)o.rho[0], o.npts, u,
+              o.pieces, c + s0 * nobs, ncv, M, out + s0 * M);
         });
       });
     });
   });
 }
 
-// launcher behind hgp_kuf_semi_mc_matvec_win / hgp_kuf_semi_sqexp_matvec_win
-hipError_t kuf_line_matvec_win(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m,
-                               const void* const* grids, const void* x, int64_t nobs, double sig2, double ell,
-                               double rho, int npts, const void* u, const int* pieces, const void* w, int64_t nw,
-                               void* out, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_line_matvec_win_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, w,
-                                        nw, out, s);
-  return kuf_line_matvec_win_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, w, nw,
-                                       out, s);
+// launchers behind hgp_kuf_semi_{mc,sqexp}_matvec_win and hgp_kuf_semi_{mc,sqexp}_rmatvec_win
+hipError_t kuf_line_matvec_win(const KufObs& o, const void* w, int64_t nw, void* out) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_line_matvec_win_t<decltype(t)>(o, w, nw, out); });
 }
 
-// launcher behind hgp_kuf_semi_mc_rmatvec_win / hgp_kuf_semi_sqexp_rmatvec_win
-hipError_t kuf_line_rmatvec_win(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m,
-                                const void* const* grids, const void* x, int64_t nobs, double sig2, double ell,
-                                double rho, int npts, const void* u, const int* pieces, const void* c, int64_t nc,
-                                void* out, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_line_rmatvec_win_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, c,
-                                         nc, out, s);
-  return kuf_line_rmatvec_win_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, rho, npts, u, pieces, c,
-                                        nc, out, s);
+hipError_t kuf_line_rmatvec_win(const KufObs& o, const void* c, int64_t nc, void* out) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_line_rmatvec_win_t<decltype(t)>(o, c, nc, out); });
 }
 
 }  // namespace hgp

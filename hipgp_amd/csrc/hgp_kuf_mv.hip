@@ -192,19 +192,18 @@ __global__ __launch_bounds__(MV_THREADS) void k_kuf_semi_mv(KufGrid g, const T* 
   }
 }
 
-// mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs > 0, nw > 0, nsplit >= 0.
+// nobs > 0, nw > 0, nsplit >= 0
 template <typename T>
-static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                               const void* xv, int64_t nobs, double sig2, const double* ell3, int npts,
-                               const void* uv, const void* wv, int64_t nw, int64_t nsplit_in, void* outv,
-                               hipStream_t s) {
-  const double ell = ell3[0];                                // the line integrals' one length scale
+static hipError_t kuf_matvec_t(const KufObs& o, const void* wv, int64_t nw, int64_t nsplit_in, void* outv) {
+  const int mode = o.mode;
+  const int64_t nobs = o.nobs;
+  hipStream_t s = o.stream;
   KufGrid g{};
   int64_t M, outer;
-  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
-  const T* x = reinterpret_cast<const T*>(xv);
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, &M, &outer);
+  const T* x = reinterpret_cast<const T*>(o.x);
   const T* w = reinterpret_cast<const T*>(wv);
-  const T* u = reinterpret_cast<const T*>(uv);
+  const T* u = reinterpret_cast<const T*>(o.u);
   T* out = reinterpret_cast<T*>(outv);
   // the split: a pure function of (nobs, M, nw) and the CU count unless the caller forces it
   const int64_t nunit = mode == 0 ? (M + MV_UNIT - 1) / MV_UNIT : outer;
@@ -229,16 +228,16 @@ static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const in
         T* og = out + s0;
         kuf_with_width(NW, [&](auto W) {
           if (mode == 0)
-            kuf_with_kind(kind, [&](auto K) {
+            kuf_with_kind(o.kind, [&](auto K) {
               hipLaunchKernelGGL((k_kuf_grid_mv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(MV_TILE),
-                                 0, s, g, x, nobs, (T)sig2, kuf_vec<T>(ell3), wg, nwv, M, (int)nsplit, nunit, part, og,
-                                 nw);
+                                 0, s, g, x, nobs, (T)o.sig2, kuf_vec<T>(o.ell), wg, nwv, M, (int)nsplit, nunit, part,
+                                 og, nw);
             });
           else
             kuf_with_mode(mode, [&](auto MD) {
               hipLaunchKernelGGL((k_kuf_semi_mv<T, decltype(MD)::value, decltype(W)::value>), dim3(nb),
-                                 dim3(MV_THREADS), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, wg, nwv, M,
-                                 (int)nsplit, part, og, nw);
+                                 dim3(MV_THREADS), 0, s, g, x, nobs, o.kind, (T)o.sig2, (T)o.ell[0], (T)o.kp, o.npts, u,
+                                 wg, nwv, M, (int)nsplit, part, og, nw);
             });
         });
       },
@@ -249,14 +248,9 @@ static hipError_t kuf_matvec_t(int mode, int kind, double kp, int ndim, const in
       });
 }
 
-// launcher behind hgp_kuf_grid_matvec(_ard) / hgp_kuf_semi_mc_matvec / hgp_kuf_semi_sqexp_matvec; ell: one value
-// per axis, three in all (a scalar entry's value in each; the line integrals read the first)
-hipError_t kuf_matvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                      const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
-                      const void* w, int64_t nw, int64_t nsplit, void* out, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_matvec_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out, s);
-  return kuf_matvec_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, w, nw, nsplit, out, s);
+// launcher behind hgp_kuf_grid_matvec(_ard) / hgp_kuf_semi_mc_matvec / hgp_kuf_semi_sqexp_matvec
+hipError_t kuf_matvec(const KufObs& o, const void* w, int64_t nw, int64_t nsplit, void* out) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_matvec_t<decltype(t)>(o, w, nw, nsplit, out); });
 }
 
 }  // namespace hgp

@@ -227,24 +227,23 @@ __global__ __launch_bounds__(RMV_TILE) void k_kuf_semi_rmv(KufGrid g, const T* _
   }
 }
 
-// mode: 0 point observations, 1 semi-mc, 2 semi-sqexp.  nobs >= 0, nc > 0, nsplit >= 0.
+// nobs >= 0, nc > 0, nsplit >= 0
 template <typename T>
-static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                                const void* xv, int64_t nobs, double sig2, const double* ell3, int npts,
-                                const void* uv, const void* cv, int64_t nc, int64_t nsplit_in, void* outv,
-                                hipStream_t s) {
-  const double ell = ell3[0];                                // the line integrals' one length scale
+static hipError_t kuf_rmatvec_t(const KufObs& o, const void* cv, int64_t nc, int64_t nsplit_in, void* outv) {
+  const int mode = o.mode;
+  const int64_t nobs = o.nobs;
+  hipStream_t s = o.stream;
   KufGrid g{};
   int64_t M, outer;
-  kuf_fill_grid(g, ndim, m, grids, &M, &outer);
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, &M, &outer);
   T* out = reinterpret_cast<T*>(outv);
   if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
-  const T* x = reinterpret_cast<const T*>(xv);
+  const T* x = reinterpret_cast<const T*>(o.x);
   const T* c = reinterpret_cast<const T*>(cv);
-  const T* u = reinterpret_cast<const T*>(uv);
+  const T* u = reinterpret_cast<const T*>(o.u);
   // the split: a pure function of (nobs, M) and the CU count unless the caller forces it; one
   // slice whenever the mesh alone gives the blocks that fill the device
-  const int64_t nchunk = (m[ndim - 1] + RMV_TILE - 1) / RMV_TILE;
+  const int64_t nchunk = (o.m[o.ndim - 1] + RMV_TILE - 1) / RMV_TILE;
   const int64_t ntile = mode == 0 ? (M + RMV_TILE - 1) / RMV_TILE : outer * nchunk;   // blocks per slice
   const int64_t nrun = (nobs + RMV_RUN - 1) / RMV_RUN;
   int64_t nsplit = nsplit_in;
@@ -264,15 +263,16 @@ static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const i
         T* og = out + s0 * M;
         kuf_with_width(NC, [&](auto W) {
           if (mode == 0)
-            kuf_with_kind(kind, [&](auto K) {
+            kuf_with_kind(o.kind, [&](auto K) {
               hipLaunchKernelGGL((k_kuf_grid_rmv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(RMV_TILE),
-                                 0, s, g, x, nobs, (T)sig2, kuf_vec<T>(ell3), cg, ncv, M, (int)nsplit, nrun, part, og);
+                                 0, s, g, x, nobs, (T)o.sig2, kuf_vec<T>(o.ell), cg, ncv, M, (int)nsplit, nrun, part,
+                                 og);
             });
           else
             kuf_with_mode(mode, [&](auto MD) {
               hipLaunchKernelGGL((k_kuf_semi_rmv<T, decltype(MD)::value, decltype(W)::value>), dim3(nb),
-                                 dim3(RMV_TILE), 0, s, g, x, nobs, kind, (T)sig2, (T)ell, (T)kp, npts, u, cg, ncv, M,
-                                 (int)nsplit, nrun, nchunk, part, og);
+                                 dim3(RMV_TILE), 0, s, g, x, nobs, o.kind, (T)o.sig2, (T)o.ell[0], (T)o.kp, o.npts, u, cg,
+                                 ncv, M, (int)nsplit, nrun, nchunk, part, og);
             });
         });
       },
@@ -283,14 +283,9 @@ static hipError_t kuf_rmatvec_t(int mode, int kind, double kp, int ndim, const i
       });
 }
 
-// launcher behind hgp_kuf_grid_rmatvec(_ard) / hgp_kuf_semi_mc_rmatvec / hgp_kuf_semi_sqexp_rmatvec; ell: one
-// value per axis, three in all (a scalar entry's value in each; the line integrals read the first)
-hipError_t kuf_rmatvec(int dtype, int mode, int kind, double kp, int ndim, const int64_t* m, const void* const* grids,
-                       const void* x, int64_t nobs, double sig2, const double* ell, int npts, const void* u,
-                       const void* c, int64_t nc, int64_t nsplit, void* out, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_rmatvec_t<float>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out, s);
-  return kuf_rmatvec_t<double>(mode, kind, kp, ndim, m, grids, x, nobs, sig2, ell, npts, u, c, nc, nsplit, out, s);
+// launcher behind hgp_kuf_grid_rmatvec(_ard) / hgp_kuf_semi_mc_rmatvec / hgp_kuf_semi_sqexp_rmatvec
+hipError_t kuf_rmatvec(const KufObs& o, const void* c, int64_t nc, int64_t nsplit, void* out) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_rmatvec_t<decltype(t)>(o, c, nc, nsplit, out); });
 }
 
 }  // namespace hgp

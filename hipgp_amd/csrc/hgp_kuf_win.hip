@@ -256,13 +256,13 @@ __global__ __launch_bounds__(WIN_THREADS) void k_kuf_win_rmv(KufGrid g, const T*
 
 // nobs > 0, nw > 0
 template <typename T>
-static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const void* const* grids, const void* xv,
-                                   int64_t nobs, double sig2, const double* ell, const double* rho, const void* wv,
-                                   int64_t nw, void* outv, hipStream_t s) {
+static hipError_t kuf_matvec_win_t(const KufObs& o, const void* wv, int64_t nw, void* outv) {
+  const int64_t nobs = o.nobs;
+  hipStream_t s = o.stream;
   KufGrid g{};
   int64_t M;
-  kuf_fill_grid(g, ndim, m, grids, &M);
-  const T* x = reinterpret_cast<const T*>(xv);
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, &M);
+  const T* x = reinterpret_cast<const T*>(o.x);
   const T* w = reinterpret_cast<const T*>(wv);
   T* out = reinterpret_cast<T*>(outv);
   const int64_t per = WIN_THREADS / 64;
@@ -270,10 +270,11 @@ static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const v
   if (nblk > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)nblk;
   return kuf_row_groups(nw, s, [&](int64_t s0, int NW, int nwv, double*) {
-    kuf_with_kind(kind, [&](auto K) {
+    kuf_with_kind(o.kind, [&](auto K) {
       kuf_with_width(NW, [&](auto W) {
         hipLaunchKernelGGL((k_kuf_win_mv<T, decltype(K)::value, decltype(W)::value>), dim3(nb), dim3(WIN_THREADS), 0,
-                           s, g, x, nobs, (T)sig2, kuf_vec<T>(ell), kuf_vec<T>(rho), w + s0 * M, nwv, M, out + s0, nw);
+                           s, g, x, nobs, (T)o.sig2, kuf_vec<T>(o.ell), kuf_vec<T>(o.rho), w + s0 * M, nwv, M,
+                           out + s0, nw);
       });
     });
   });
@@ -281,26 +282,26 @@ static hipError_t kuf_matvec_win_t(int kind, int ndim, const int64_t* m, const v
 
 // nobs >= 0 (0: out zeroed), nc > 0
 template <typename T>
-static hipError_t kuf_rmatvec_win_t(int kind, int ndim, const int64_t* m, const void* const* grids, const void* xv,
-                                    int64_t nobs, double sig2, const double* ell, const double* rho, const void* cv,
-                                    int64_t nc, const int64_t* order, const int64_t* bin_start, void* outv,
-                                    hipStream_t s) {
+static hipError_t kuf_rmatvec_win_t(const KufObs& o, const void* cv, int64_t nc, const int64_t* order,
+                                    const int64_t* bin_start, void* outv) {
+  const int64_t nobs = o.nobs;
+  hipStream_t s = o.stream;
   KufGrid g{};
   int64_t M;
-  kuf_fill_grid(g, ndim, m, grids, &M);
+  kuf_fill_grid(g, o.ndim, o.m, o.grids, &M);
   T* out = reinterpret_cast<T*>(outv);
   if (nobs == 0) return hipMemsetAsync(out, 0, (size_t)nc * (size_t)M * sizeof(T), s);   // an empty sum
-  const T* x = reinterpret_cast<const T*>(xv);
+  const T* x = reinterpret_cast<const T*>(o.x);
   const T* c = reinterpret_cast<const T*>(cv);
-  const int64_t ntile = kuf_tile_count(ndim, m);
+  const int64_t ntile = kuf_tile_count(o.ndim, o.m);
   if (ntile > 0x7fffffffLL) return hipErrorInvalidConfiguration;
   const unsigned nb = (unsigned)ntile;
   return kuf_row_groups(nc, s, [&](int64_t s0, int NC, int ncv, double*) {
-    kuf_with_kind(kind, [&](auto K) {
-      kuf_with_dim(ndim, [&](auto D) {
+    kuf_with_kind(o.kind, [&](auto K) {
+      kuf_with_dim(o.ndim, [&](auto D) {
         kuf_with_width(NC, [&](auto W) {
           hipLaunchKernelGGL((k_kuf_win_rmv<T, decltype(K)::value, decltype(W)::value, decltype(D)::value>), dim3(nb),
-                             dim3(WIN_THREADS), 0, s, g, x, nobs, (T)sig2, kuf_vec<T>(ell), kuf_vec<T>(rho),
+                             dim3(WIN_THREADS), 0, s, g, x, nobs, (T)o.sig2, kuf_vec<T>(o.ell), kuf_vec<T>(o.rho),
                              c + s0 * nobs, ncv, M, order, bin_start, out + s0 * M);
         });
       });
@@ -308,23 +309,15 @@ static hipError_t kuf_rmatvec_win_t(int kind, int ndim, const int64_t* m, const 
   });
 }
 
-// launcher behind hgp_kuf_grid_matvec_win(_ard); ell, rho: one value per axis, three each (a scalar entry's value
-// in each)
-hipError_t kuf_matvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                          int64_t nobs, double sig2, const double* ell, const double* rho, const void* w, int64_t nw,
-                          void* out, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_matvec_win_t<float>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, w, nw, out, s);
-  return kuf_matvec_win_t<double>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, w, nw, out, s);
+// launchers behind hgp_kuf_grid_matvec_win(_ard) and hgp_kuf_grid_rmatvec_win(_ard)
+hipError_t kuf_matvec_win(const KufObs& o, const void* w, int64_t nw, void* out) {
+  return kuf_with_dtype(o.dtype, [&](auto t) { return kuf_matvec_win_t<decltype(t)>(o, w, nw, out); });
 }
 
-// launcher behind hgp_kuf_grid_rmatvec_win(_ard); ell, rho as kuf_matvec_win
-hipError_t kuf_rmatvec_win(int dtype, int kind, int ndim, const int64_t* m, const void* const* grids, const void* x,
-                           int64_t nobs, double sig2, const double* ell, const double* rho, const void* c, int64_t nc,
-                           const int64_t* order, const int64_t* bin_start, void* out, hipStream_t s) {
-  if (dtype == HGP_F32)
-    return kuf_rmatvec_win_t<float>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, c, nc, order, bin_start, out, s);
-  return kuf_rmatvec_win_t<double>(kind, ndim, m, grids, x, nobs, sig2, ell, rho, c, nc, order, bin_start, out, s);
+hipError_t kuf_rmatvec_win(const KufObs& o, const void* c, int64_t nc, const int64_t* order,
+                           const int64_t* bin_start, void* out) {
+  return kuf_with_dtype(o.dtype,
+                        [&](auto t) { return kuf_rmatvec_win_t<decltype(t)>(o, c, nc, order, bin_start, out); });
 }
 
 // the geometry behind hgp_kuf_win_bins: tile[a] mesh points of a tile along axis a, nbins[a] =

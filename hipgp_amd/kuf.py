@@ -59,18 +59,25 @@ def _scalar(v):
     return float(v)
 
 
+def _ell_form(v, D):
+    """0 for a scalar ell (a number, or a tensor of one element), 1 for one length scale per axis (a 1-D
+    tensor or a sequence of length D), else None; no value is read."""
+    if torch.is_tensor(v):
+        return 0 if v.numel() == 1 else 1 if v.dim() == 1 and v.numel() == D else None
+    if isinstance(v, (list, tuple)):
+        return 1 if len(v) == D else None
+    return 0
+
+
 def _ell_arg(v, D):
     """ell as the fused kernels take it: a float for a scalar (number, or tensor of one element), a
     list of D floats for a 1-D tensor or sequence of length D (one length scale per axis), else None."""
-    if torch.is_tensor(v):
-        if v.numel() == 1:
-            return _scalar(v)
-        if v.dim() == 1 and v.numel() == D:
-            return [float(e) for e in v.detach().cpu().tolist()]
+    form = _ell_form(v, D)
+    if form is None:
         return None
-    if isinstance(v, (list, tuple)):
-        return [float(e) for e in v] if len(v) == D else None
-    return float(v)
+    if form == 0:
+        return _scalar(v)
+    return [float(e) for e in (v.detach().cpu().tolist() if torch.is_tensor(v) else v)]
 
 
 def _is_ard(el):
@@ -89,66 +96,95 @@ def _dvec(vals):
     return (ctypes.c_double * len(vals))(*vals)
 
 
-def kuf_grid(kernel, xgrids, x, params):
-    """Knm (nobs, M) for observations x (nobs, D) against the C-order mesh of xgrids, or None
-    when the fused path does not apply (caller then evaluates the torch kernel)."""
-    kind = kernel_kind(kernel)
-    if kind is None or x.device.type != "cuda" or x.dim() != 2 or x.shape[1] != len(xgrids):
-        return None
-    if x.dtype not in (torch.float32, torch.float64) or len(xgrids) > 3:
-        return None
-    sig2, ell = params
-    if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in (sig2, ell, x)):
-        return None
-    s2, el = _scalar(sig2), _ell_arg(ell, len(xgrids))
-    if s2 is None or el is None or (_is_ard(el) and not _takes_ard(kernel)):
-        return None
-    grids = [g.to(device=x.device, dtype=x.dtype).contiguous() for g in xgrids]
-    xc = x.detach().contiguous()
-    M = 1
-    for g in grids:
-        M *= g.numel()
-    out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
-    m = (ctypes.c_int64 * len(grids))(*[g.numel() for g in grids])
-    ptrs = (ctypes.c_void_p * len(grids))(*[g.data_ptr() for g in grids])
-    if _is_ard(el):
-        check(lib().hgp_kuf_grid_ard(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
-                                     ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, _dvec(el),
-                                     ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-        return out
-    check(lib().hgp_kuf_grid(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
-                             x.shape[0], s2, el, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
-
-
-def _grid_call_args(kernel, xgrids, x, params, gneiting=False, ard=False):
-    """(kind, s2, el, grids, xc, M) for the fused grid kernels, or None when they do not apply.  el is
-    a float; with `ard` (the point functions) a list of one float per axis for a vector ell, which
-    a SqExp declared with ard=True alone takes."""
+def _gate(kernel, xgrids, x, params, gneiting=False, ard=False, graph=False):
+    """The HGP_KERN_* code, or None where the fused kernels decline: a kernel without a fused forward
+    (`gneiting`: the Monte-Carlo line integral also takes Gneiting), a CPU tensor, x not (nobs, D <= 3)
+    in fp32 / fp64, a non-scalar sig2, an ell that is neither a scalar nor -- with `ard` (the point
+    functions), for a SqExp declared with ard=True -- one value per axis, a graph to x, and a graph to
+    sig2 or ell unless that graph is the point (`graph`: the `_ad` functions)."""
     kind = kernel_kind(kernel, gneiting=gneiting)
     if kind is None or x.device.type != "cuda" or x.dim() != 2 or x.shape[1] != len(xgrids):
         return None
     if x.dtype not in (torch.float32, torch.float64) or len(xgrids) > 3:
         return None
     sig2, ell = params
-    if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in (sig2, ell, x)):
+    if torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad
+                                       for p in ((x,) if graph else (sig2, ell, x))):
         return None
-    s2, el = _scalar(sig2), _ell_arg(ell, len(xgrids))
-    if s2 is None or el is None:
+    if torch.is_tensor(sig2) and sig2.numel() != 1:
         return None
-    if _is_ard(el) and not (ard and _takes_ard(kernel)):
+    form = _ell_form(ell, len(xgrids))
+    if form is None:
+        return None
+    if form == 1 and not (ard and _takes_ard(kernel)):
+        return None
+    return kind
+
+
+def _grid_call_args(kernel, xgrids, x, params, gneiting=False, ard=False):
+    """(kind, s2, el, grids, xc, M) for the fused grid kernels, or None when they do not apply (`_gate`).
+    el is a float, or a list of one float per axis for a vector ell."""
+    kind = _gate(kernel, xgrids, x, params, gneiting=gneiting, ard=ard)
+    if kind is None:
         return None
     grids = [g.to(device=x.device, dtype=x.dtype).contiguous() for g in xgrids]
     M = 1
     for g in grids:
         M *= g.numel()
-    return kind, s2, el, grids, x.detach().contiguous(), M
+    return kind, _scalar(params[0]), _ell_arg(params[1], len(grids)), grids, x.detach().contiguous(), M
 
 
 def _grid_ptrs(grids):
     m = (ctypes.c_int64 * len(grids))(*[g.numel() for g in grids])
     ptrs = (ctypes.c_void_p * len(grids))(*[g.data_ptr() for g in grids])
     return m, ptrs
+
+
+def _ptr(t):
+    return ctypes.c_void_p(None if t is None else t.data_ptr())
+
+
+def _offset_draw(u, dtype, x):
+    """The Monte-Carlo offset as the entries take it, one element on x's device in x's dtype: the given
+    `u`, or one torch.rand(1) draw in the kernel's dtype exactly as the reference (`kernels.py:28-29`).
+    Called after every way of declining, so that a declined call consumes nothing."""
+    if u is None:
+        u = torch.rand(1, dtype=dtype, device=x.device)
+    return u.detach().to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
+
+
+def _kuf_head(x, grids, s2, el, pre=(), rho=None, mc=None):
+    """(ard, head) of one hgp_kuf_* entry: head is what follows dtype, `pre` (the entry's kind, or kind and
+    kp, if it takes them), ndim, m, grids, x, nobs, sig2, ell, [rho], [npts, u] with mc = (npts, u).  A list
+    ell (and rho) goes as host doubles and `ard` says that the entry named *_ard reads them."""
+    m, ptrs = _grid_ptrs(grids)
+    ard = _is_ard(el)
+    head = [*pre, len(grids), m, ptrs, _ptr(x), x.shape[0], s2, _dvec(el) if ard else el]
+    if rho is not None:
+        head.append(_dvec(rho) if ard else rho)
+    if mc is not None:
+        head += (int(mc[0]), _ptr(mc[1]))
+    return ard, head
+
+
+def _kuf_call(name, out, x, grids, s2, el, *tail, **head):
+    """Run one hgp_kuf_* entry (`name`, or name_ard for a list ell): dtype, `_kuf_head`, the entry's own
+    `tail` as ctypes values, then `out` and the stream.  Returns `out`."""
+    ard, args = _kuf_head(x, grids, s2, el, **head)
+    check(getattr(lib(), name + "_ard" if ard else name)(_lib.dtype_code(x.dtype), *args, *tail, _ptr(out),
+                                                         _lib.stream_ptr(x.device)))
+    return out
+
+
+def kuf_grid(kernel, xgrids, x, params):
+    """Knm (nobs, M) for observations x (nobs, D) against the C-order mesh of xgrids, or None
+    when the fused path does not apply (caller then evaluates the torch kernel)."""
+    a = _grid_call_args(kernel, xgrids, x, params, ard=True)
+    if a is None:
+        return None
+    kind, s2, el, grids, xc, M = a
+    out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
+    return _kuf_call("hgp_kuf_grid", out, xc, grids, s2, el, pre=(kind,))
 
 
 def kuf_semi_mc(kernel, xgrids, x, params, npts, u=None):
@@ -160,17 +196,9 @@ def kuf_semi_mc(kernel, xgrids, x, params, npts, u=None):
     if a is None:
         return None
     kind, s2, el, grids, xc, M = a
-    if u is None:
-        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
-    u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
     out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    kp = float(getattr(kernel, "alpha", 1.))
-    check(lib().hgp_kuf_semi_mc(_lib.dtype_code(x.dtype), kind, kp, len(grids), m, ptrs,
-                                ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el, int(npts),
-                                ctypes.c_void_p(u.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_semi_mc", out, xc, grids, s2, el,
+                     pre=(kind, float(getattr(kernel, "alpha", 1.))), mc=(npts, _offset_draw(u, kernel.dtype, x)))
 
 
 def kuf_semi_sqexp(kernel, xgrids, x, params):
@@ -181,10 +209,7 @@ def kuf_semi_sqexp(kernel, xgrids, x, params):
         return None
     kind, s2, el, grids, xc, M = a
     out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    check(lib().hgp_kuf_semi_sqexp(_lib.dtype_code(x.dtype), len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
-                                   x.shape[0], s2, el, ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_semi_sqexp", out, xc, grids, s2, el)
 
 
 # ---- products with the cross covariances, Knm never stored (hgp_kuf_*_matvec) -------------------
@@ -214,17 +239,7 @@ def kuf_grid_matvec(kernel, xgrids, x, params, W, nsplit=0):
     if Wc is None:
         return None
     out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    if _is_ard(el):
-        check(lib().hgp_kuf_grid_matvec_ard(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
-                                            ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, _dvec(el),
-                                            ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
-                                            ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-        return out
-    check(lib().hgp_kuf_grid_matvec(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
-                                    x.shape[0], s2, el, ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
-                                    ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_grid_matvec", out, xc, grids, s2, el, _ptr(Wc), Wc.shape[0], int(nsplit), pre=(kind,))
 
 
 def kuf_semi_mc_matvec(kernel, xgrids, x, params, npts, u=None, W=None, nsplit=0):
@@ -239,17 +254,9 @@ def kuf_semi_mc_matvec(kernel, xgrids, x, params, npts, u=None, W=None, nsplit=0
     Wc = _matvec_weights(W, x, M)
     if Wc is None:
         return None
-    if u is None:
-        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
-    u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
     out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    kp = float(getattr(kernel, "alpha", 1.))
-    check(lib().hgp_kuf_semi_mc_matvec(_lib.dtype_code(x.dtype), kind, kp, len(grids), m, ptrs,
-                                       ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el, int(npts),
-                                       ctypes.c_void_p(u.data_ptr()), ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0],
-                                       int(nsplit), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_semi_mc_matvec", out, xc, grids, s2, el, _ptr(Wc), Wc.shape[0], int(nsplit),
+                     pre=(kind, float(getattr(kernel, "alpha", 1.))), mc=(npts, _offset_draw(u, kernel.dtype, x)))
 
 
 def kuf_semi_sqexp_matvec(kernel, xgrids, x, params, W, nsplit=0):
@@ -263,11 +270,7 @@ def kuf_semi_sqexp_matvec(kernel, xgrids, x, params, W, nsplit=0):
     if Wc is None:
         return None
     out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    check(lib().hgp_kuf_semi_sqexp_matvec(_lib.dtype_code(x.dtype), len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
-                                          x.shape[0], s2, el, ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], int(nsplit),
-                                          ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_semi_sqexp_matvec", out, xc, grids, s2, el, _ptr(Wc), Wc.shape[0], int(nsplit))
 
 
 # ---- products with the transposed cross covariances, Knm never stored (hgp_kuf_*_rmatvec) -------
@@ -297,18 +300,7 @@ def kuf_grid_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
     if Cc is None:
         return None
     out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    if _is_ard(el):
-        check(lib().hgp_kuf_grid_rmatvec_ard(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
-                                             ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, _dvec(el),
-                                             ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
-                                             ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-        return out
-    check(lib().hgp_kuf_grid_rmatvec(_lib.dtype_code(x.dtype), kind, len(grids), m, ptrs,
-                                     ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el,
-                                     ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
-                                     ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_grid_rmatvec", out, xc, grids, s2, el, _ptr(Cc), Cc.shape[0], int(nsplit), pre=(kind,))
 
 
 def kuf_semi_mc_rmatvec(kernel, xgrids, x, params, npts, u=None, C=None, nsplit=0):
@@ -323,17 +315,9 @@ def kuf_semi_mc_rmatvec(kernel, xgrids, x, params, npts, u=None, C=None, nsplit=
     Cc = _rmatvec_coefs(C, x)
     if Cc is None:
         return None
-    if u is None:
-        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
-    u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
     out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    kp = float(getattr(kernel, "alpha", 1.))
-    check(lib().hgp_kuf_semi_mc_rmatvec(_lib.dtype_code(x.dtype), kind, kp, len(grids), m, ptrs,
-                                        ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el, int(npts),
-                                        ctypes.c_void_p(u.data_ptr()), ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0],
-                                        int(nsplit), ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_semi_mc_rmatvec", out, xc, grids, s2, el, _ptr(Cc), Cc.shape[0], int(nsplit),
+                     pre=(kind, float(getattr(kernel, "alpha", 1.))), mc=(npts, _offset_draw(u, kernel.dtype, x)))
 
 
 def kuf_semi_sqexp_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
@@ -347,12 +331,7 @@ def kuf_semi_sqexp_rmatvec(kernel, xgrids, x, params, C, nsplit=0):
     if Cc is None:
         return None
     out = torch.empty((Cc.shape[0], M), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(grids)
-    check(lib().hgp_kuf_semi_sqexp_rmatvec(_lib.dtype_code(x.dtype), len(grids), m, ptrs,
-                                           ctypes.c_void_p(xc.data_ptr()), x.shape[0], s2, el,
-                                           ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], int(nsplit),
-                                           ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_semi_sqexp_rmatvec", out, xc, grids, s2, el, _ptr(Cc), Cc.shape[0], int(nsplit))
 
 
 # ---- the same two products over a window: kernels far shorter than the grid ----------------------
@@ -510,18 +489,8 @@ def kuf_grid_matvec_win(plan, W):
     if Wc is None:
         return None
     out = torch.empty((x.shape[0], Wc.shape[0]), dtype=x.dtype, device=x.device)
-    m, ptrs = _grid_ptrs(plan.grids)
-    if _is_ard(plan.ell):
-        check(lib().hgp_kuf_grid_matvec_win_ard(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
-                                                ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, _dvec(plan.ell),
-                                                _dvec(plan.rho), ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0],
-                                                ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-        return out
-    check(lib().hgp_kuf_grid_matvec_win(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
-                                        ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho,
-                                        ctypes.c_void_p(Wc.data_ptr()), Wc.shape[0], ctypes.c_void_p(out.data_ptr()),
-                                        _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_grid_matvec_win", out, x, plan.grids, plan.sig2, plan.ell, _ptr(Wc), Wc.shape[0],
+                     pre=(plan.kind,), rho=plan.rho)
 
 
 def kuf_grid_rmatvec_win(plan, C):
@@ -535,20 +504,8 @@ def kuf_grid_rmatvec_win(plan, C):
         return None
     out = torch.empty((Cc.shape[0], plan.M), dtype=x.dtype, device=x.device)
     order, start = plan.bins() if x.shape[0] > 0 else (None, None)
-    m, ptrs = _grid_ptrs(plan.grids)
-    ptr = lambda t: ctypes.c_void_p(None if t is None else t.data_ptr())
-    if _is_ard(plan.ell):
-        check(lib().hgp_kuf_grid_rmatvec_win_ard(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
-                                                 ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2,
-                                                 _dvec(plan.ell), _dvec(plan.rho), ctypes.c_void_p(Cc.data_ptr()),
-                                                 Cc.shape[0], ptr(order), ptr(start),
-                                                 ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-        return out
-    check(lib().hgp_kuf_grid_rmatvec_win(_lib.dtype_code(x.dtype), plan.kind, len(plan.grids), m, ptrs,
-                                         ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho,
-                                         ctypes.c_void_p(Cc.data_ptr()), Cc.shape[0], ptr(order), ptr(start),
-                                         ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(x.device)))
-    return out
+    return _kuf_call("hgp_kuf_grid_rmatvec_win", out, x, plan.grids, plan.sig2, plan.ell, _ptr(Cc), Cc.shape[0],
+                     _ptr(order), _ptr(start), pre=(plan.kind,), rho=plan.rho)
 
 
 # ---- the two line-integral products over the window of a line: a tube around its segment --------
@@ -606,19 +563,9 @@ class LineWindowPlan:
 
 def _line_win_call(plan, name, rows, out, npts=None, u=None):
     """One hgp_kuf_semi_*_win entry: `rows` are the weight or coefficient rows."""
-    x = plan.x
-    m, ptrs = _grid_ptrs(plan.grids)
-    head = [_lib.dtype_code(x.dtype)] + ([plan.kind] if npts is not None else []) + \
-           [len(plan.grids), m, ptrs, ctypes.c_void_p(x.data_ptr()), x.shape[0], plan.sig2, plan.ell, plan.rho]
-    if npts is not None:
-        if u is None:
-            u = torch.rand(1, dtype=plan.kernel_dtype, device=x.device)         # kernels.py:28-29
-        u = u.to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
-        head += [int(npts), ctypes.c_void_p(u.data_ptr())]
-    check(getattr(lib(), name)(*head, ctypes.c_void_p(plan.pieces.data_ptr()), plan.pieces.shape[0],
-                               ctypes.c_void_p(rows.data_ptr()), rows.shape[0], ctypes.c_void_p(out.data_ptr()),
-                               _lib.stream_ptr(x.device)))
-    return out
+    mc = {} if npts is None else dict(pre=(plan.kind,), mc=(npts, _offset_draw(u, plan.kernel_dtype, plan.x)))
+    return _kuf_call(name, out, plan.x, plan.grids, plan.sig2, plan.ell, _ptr(plan.pieces), plan.pieces.shape[0],
+                     _ptr(rows), rows.shape[0], rho=plan.rho, **mc)
 
 
 def kuf_semi_mc_matvec_win(plan, W, npts, u=None):
@@ -721,18 +668,10 @@ def _ad_route(kernel, xgrids, x, params, ard=False):
     hyper-parameter gradient is asked for (the plain forward serves); else the HGP_KERN_* code.
     ard: a 1-D ell tensor with one entry per axis passes for a SqExp declared with ard=True (the point
     function alone)."""
-    if xgrids is None or not torch.is_tensor(x) or x.requires_grad and torch.is_grad_enabled():
+    if xgrids is None or not torch.is_tensor(x):
         return None
-    kind = kernel_kind(kernel)                       # no Gneiting: its gradient is NaN at r = 0
-    if kind is None or x.device.type != "cuda" or x.dim() != 2 or x.shape[1] != len(xgrids):
-        return None
-    if x.dtype not in (torch.float32, torch.float64) or len(xgrids) > 3:
-        return None
-    sig2, ell = params
-    if torch.is_tensor(sig2) and sig2.numel() != 1:
-        return None
-    if torch.is_tensor(ell) and ell.numel() != 1 and \
-            not (ard and _takes_ard(kernel) and ell.dim() == 1 and ell.numel() == len(xgrids)):
+    kind = _gate(kernel, xgrids, x, params, ard=ard, graph=True)     # no Gneiting: its gradient is NaN at r = 0
+    if kind is None:
         return None
     if not (torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in params)):
         return False
@@ -766,12 +705,9 @@ def kuf_grid_ad(kernel, xgrids, x, params):
     grids, xc = _ad_inputs(xgrids, x)
 
     def bwd(s2, el, G):
-        m, ptrs = _grid_ptrs(grids)
-        if _is_ard(el):
-            return _grad_call(lib().hgp_kuf_grid_grad_ard, xc, G, kind, len(grids), m, ptrs,
-                              ctypes.c_void_p(xc.data_ptr()), xc.shape[0], s2, _dvec(el), nsum=1 + len(el))
-        return _grad_call(lib().hgp_kuf_grid_grad, xc, G, kind, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
-                          xc.shape[0], s2, el)
+        ard, head = _kuf_head(xc, grids, s2, el, pre=(kind,))
+        return _grad_call(lib().hgp_kuf_grid_grad_ard if ard else lib().hgp_kuf_grid_grad, xc, G, *head,
+                          nsum=1 + len(el) if ard else 2)
     return _KufAD.apply(params[0], params[1], lambda s2, el: kuf_grid(kernel, grids, xc, (s2, el)), bwd)
 
 
@@ -784,15 +720,11 @@ def kuf_semi_mc_ad(kernel, xgrids, x, params, npts, u=None):
     if kind is False:
         return kuf_semi_mc(kernel, xgrids, x, params, npts, u=u)
     grids, xc = _ad_inputs(xgrids, x)
-    if u is None:
-        u = torch.rand(1, dtype=kernel.dtype, device=x.device)          # kernels.py:28-29
-    uc = u.detach().to(device=x.device, dtype=x.dtype).reshape(1).contiguous()
+    uc = _offset_draw(u, kernel.dtype, x)
 
     def bwd(s2, el, G):
-        m, ptrs = _grid_ptrs(grids)
-        return _grad_call(lib().hgp_kuf_semi_mc_grad, xc, G, kind, 1., len(grids), m, ptrs,
-                          ctypes.c_void_p(xc.data_ptr()), xc.shape[0], s2, el, int(npts),
-                          ctypes.c_void_p(uc.data_ptr()))
+        return _grad_call(lib().hgp_kuf_semi_mc_grad, xc, G,
+                          *_kuf_head(xc, grids, s2, el, pre=(kind, 1.), mc=(npts, uc))[1])
     return _KufAD.apply(params[0], params[1],
                         lambda s2, el: kuf_semi_mc(kernel, grids, xc, (s2, el), npts, u=uc), bwd)
 
@@ -807,9 +739,7 @@ def kuf_semi_sqexp_ad(kernel, xgrids, x, params):
     grids, xc = _ad_inputs(xgrids, x)
 
     def bwd(s2, el, G):
-        m, ptrs = _grid_ptrs(grids)
-        return _grad_call(lib().hgp_kuf_semi_sqexp_grad, xc, G, len(grids), m, ptrs, ctypes.c_void_p(xc.data_ptr()),
-                          xc.shape[0], s2, el)
+        return _grad_call(lib().hgp_kuf_semi_sqexp_grad, xc, G, *_kuf_head(xc, grids, s2, el)[1])
     return _KufAD.apply(params[0], params[1], lambda s2, el: kuf_semi_sqexp(kernel, grids, xc, (s2, el)), bwd)
 
 
